@@ -4,7 +4,7 @@
 all-reduce) at the WSJ shape of BASELINE.json configs[2]:
 T=1000, |alphabet|=33, 5x1824 BRNN (temporalLayer 3, inputDim 483), U=100, minibatch 32 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: either under a launcher -- python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
      --gpus N ... -- or plain: without RANK / WORLD_SIZE in the environment the script starts that launcher itself)
 
@@ -15,11 +15,18 @@ processes its own 32 utterances; the only exchange is the sum of the weight grad
 The metric is SURVEY 8(d)'s: the features of a step start in PINNED HOST memory; their H2D copy
 runs on a copy stream into one of two device buffers, so the upload of step k+1 overlaps the
 compute of step k (all K uploads sit inside the timed region).  `value` = frames / wall time of
-exactly K such steps (barrier + synchronize on both sides, max over ranks).  The same K steps with
-the features already RESIDENT in HBM are the side field `hbm_resident` (what the kernels alone
-do; round 3 reported that as `value`, rounds 1-2 and 4 the pinned-host pipeline), both step times
-are repeated in `timing` at the head of the line.  One utterance's cost is checked against the
-float64 oracle outside the timed region: a mismatch fails the run.
+exactly K such steps (barrier + synchronize on both sides, max over ranks), `ms_per_step` = that
+wall time / K.  A plain run does only that: set-up, W warm-up steps, the K timed steps, the line.
+--dump-outputs DIR writes what the last timed step returned to its caller (dump_outputs); the
+inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything else, outside the timed region unless said otherwise: the CPU baseline
+(before the HIP runtime starts), phase timers during the K timed steps (the roofline legs), the
+same K steps with the features already RESIDENT in HBM (side field `hbm_resident`: what the
+kernels alone do; round 3 reported that as `value`, rounds 1-2 and 4 the pinned-host pipeline),
+one utterance's cost checked against the float64 oracle (a mismatch fails the run), the side
+measurements and other configurations (--no-side / --no-cpu-baseline leave parts out), and for
+N>1 the exchange's timing and the N = 1 step time it is compared with.
 """
 import argparse
 import ctypes
@@ -174,6 +181,31 @@ def oracle_cost_check(cfg, net, feats_one, labels_one, cost_gpu):
     return {"utterance": 0, "gpu": float(cost_gpu), "oracle": float(c_ref), "rel_err": float(err)}
 
 
+DUMP_SAMPLE = 1 << 20       # entries kept of a gradient matrix larger than this
+
+
+def dump_outputs(d, net, cost, skip):
+    """--dump-outputs: what the last timed step returned to its caller (costAndGradBatch: cost, grad stack, skip), one
+    DIR/<name>.npy each -- cost (float64 [B]), skip (float32 0 / 1 [B]), grad_W<i> / grad_b<i> for the NL + 1
+    feed-forward layers and grad_Wf / grad_Wb of the temporal layer (float32).  The whole gradient is 84 MB at the
+    headline shape: a matrix of more than DUMP_SAMPLE entries is written as DUMP_SAMPLE of them, at row-major positions
+    drawn from a fixed seed and sorted (the same positions in every run), 28 MB in all."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"cost": np.asarray(cost, dtype=np.float64), "skip": np.asarray(skip, dtype=np.float32)}
+    NL = net.numLayers
+    for i, (w, b) in enumerate(net.grad):
+        if i <= NL:
+            arrays["grad_W%d" % (i + 1)] = w.copy_to_host()
+            arrays["grad_b%d" % (i + 1)] = b.copy_to_host()
+        else:                                       # the temporal pair's bias is a shared dummy, not a gradient
+            arrays["grad_W%s" % ("f" if i == NL + 1 else "b")] = w.copy_to_host()
+    for name, a in arrays.items():
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(7).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher around it (no RANK / WORLD_SIZE in the environment): re-run
     this very command line under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1 and a
@@ -210,13 +242,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, roofline, oracle cost check, side measurements and other "
+                         "configurations (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the PCIe-inclusive and ragged side measurements (profiling runs)")
+                    help="--full without the PCIe-inclusive, ragged and other side measurements (profiling runs)")
     ap.add_argument("--batch", type=int, default=CFG["B"], help="utterances per GPU")
     ap.add_argument("--n1-ms", type=float, default=None,
-                    help="N > 1: the single-GPU step time (ms, HBM-resident features) to compare with; default: measured "
-                         "in this run, every rank stepping alone on its own GPU before the data-parallel steps")
+                    help="--full, N > 1: the single-GPU step time (ms, HBM-resident features) to compare with; default: "
+                         "measured in this run, every rank stepping alone on its own GPU before the data-parallel steps")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -226,7 +263,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # the CPU legs fork worker processes: run them before the HIP runtime exists in this process
-    cpu_base = cpu_baseline(dict(CFG)) if (world == 1 and not args.no_cpu_baseline) else None
+    cpu_base = cpu_baseline(dict(CFG)) if (args.full and world == 1 and not args.no_cpu_baseline) else None
     import torch
     import torch.distributed as dist
     if not torch.cuda.is_available():
@@ -320,9 +357,10 @@ def main():
 
     # roofline leg: asynchronous phase timers (sctc_brnn_set_profiling(h, 2)) -- one hipEvent per
     # kernel group on the compute stream, resolved after each step (every step ends in a host sync
-    # anyway: the costs come back); no sync is added inside a step, so they run DURING the timed steps
+    # anyway: the costs come back); no sync is added inside a step, so they run DURING the timed steps (--full only)
     Lp = _sctc.lib()
-    Lp.sctc_brnn_set_profiling(net._h, 2)
+    if args.full:
+        Lp.sctc_brnn_set_profiling(net._h, 2)
     phase_acc = np.zeros(len(PHASES))
     phase_arr = (ctypes.c_float * len(PHASES))()
 
@@ -351,7 +389,7 @@ def main():
 
     comm_acc = []
     n1_ms = args.n1_ms
-    if dp is not None and n1_ms is None:
+    if args.full and dp is not None and n1_ms is None:
         # what ONE GPU does alone with the same per-GPU minibatch (no exchange, HBM-resident features): every rank steps
         # on its own device at the same time, rank 0's figure is the N = 1 leg of scaling_efficiency_vs_n1
         net.costAndGradBatch(None, labels, feats_dev=feats, T_b=Ts)
@@ -365,21 +403,25 @@ def main():
     if args.warmup:
         run_steps(args.warmup, resident=False)
     fence()
-    if dp is not None:
+    if dp is not None and args.full:
         dp.time_comm = True
     t0 = time.perf_counter()
-    cost, skip, step_ev = run_steps(args.steps, resident=False, collect=True)
+    cost, skip, step_ev = run_steps(args.steps, resident=False, collect=args.full)
     fence()
     elapsed = time.perf_counter() - t0
     if dp is not None:
         dp.time_comm = False
-    # side field: the same K steps with the features already resident in HBM
-    run_steps(1, resident=True)
-    fence()
-    t0 = time.perf_counter()
-    run_steps(args.steps, resident=True)
-    fence()
-    elapsed_res = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, net, cost, skip)
+    elapsed_res = 0.0
+    if args.full:
+        # side field: the same K steps with the features already resident in HBM
+        run_steps(1, resident=True)
+        fence()
+        t0 = time.perf_counter()
+        run_steps(args.steps, resident=True)
+        fence()
+        elapsed_res = time.perf_counter() - t0
     per_step_ms = sorted(step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps))
     if dp is not None:
         t = torch.tensor([elapsed, elapsed_res], dtype=torch.float64, device="cuda")
@@ -392,6 +434,28 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "audio frames/sec (CTC fwd-bwd + BRNN grad) at T=1000, L=5, H=1824, |Sigma|=33",
+            "value": frames_total / elapsed, "unit": "frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "timing": {"value_is": "pinned_host_overlapped", "pinned_host_overlapped_ms": ms_per_step},
+            "config": {"workload": "WSJ-shape cfg-3: T=1000 A=33 5x1824 BRNN (temporalLayer 3, "
+                                   "inputDim 483) U=100, minibatch %d per GPU, one costAndGrad per "
+                                   "step" % B,
+                       "utterances_per_gpu": B, "frames_per_step": world * B * T,
+                       "parallelism": ("dp%d (utterances sharded, per-layer RCCL all-reduce of the "
+                                       "weight gradients overlapped with the backward pass)" % world)
+                                      if dp is not None else "single-gpu",
+                       "backend": backend if dp is not None else None,
+                       "rccl_ranks": (["%d:%s:%s" % (r, i[0], i[1]) for r, i in enumerate(dp.device_ids)]
+                                      if dp is not None else None),
+                       "shared_device_mode": bool(dp.shared_device) if dp is not None else False},
+            "ms_per_step_median": median_ms,
+            "cost_mean": float(np.mean(cost[~skip])) if (~skip).any() else None,
+        }
+    if rank == 0 and args.full:
         # ---- roofline leg: the phase times of the K timed steps themselves
         L = _sctc.lib()
         ph = dict(zip(PHASES, [float(v) for v in phase_acc / max(1, args.steps)]))
@@ -412,26 +476,9 @@ def main():
         n_gemm_launches = (NL + 1) + (NL + 1) + NL + 2
         achieved = gm.value / (gemm_ms * 1e-3) / 1e12
         ctc_bytes = B * (2 * 4 * A * T + 4 * U + 8)
-        out = {
-            "metric": "audio frames/sec (CTC fwd-bwd + BRNN grad) at T=1000, L=5, H=1824, |Sigma|=33",
-            "value": frames_total / elapsed, "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "timing": {"value_is": "pinned_host_overlapped", "pinned_host_overlapped_ms": ms_per_step,
-                       "hbm_resident_ms": elapsed_res / args.steps * 1e3,
-                       "hbm_resident_frames_per_s": frames_total / elapsed_res},
-            "config": {"workload": "WSJ-shape cfg-3: T=1000 A=33 5x1824 BRNN (temporalLayer 3, "
-                                   "inputDim 483) U=100, minibatch %d per GPU, one costAndGrad per "
-                                   "step" % B,
-                       "utterances_per_gpu": B, "frames_per_step": world * B * T,
-                       "parallelism": ("dp%d (utterances sharded, per-layer RCCL all-reduce of the "
-                                       "weight gradients overlapped with the backward pass)" % world)
-                                      if dp is not None else "single-gpu",
-                       "backend": backend if dp is not None else None,
-                       "rccl_ranks": (["%d:%s:%s" % (r, i[0], i[1]) for r, i in enumerate(dp.device_ids)]
-                                      if dp is not None else None),
-                       "shared_device_mode": bool(dp.shared_device) if dp is not None else False},
+        out["timing"].update({"hbm_resident_ms": elapsed_res / args.steps * 1e3,
+                              "hbm_resident_frames_per_s": frames_total / elapsed_res})
+        out.update({
             "roofline": {"bound": "mfma", "kernel": "gemm_f32_kernel (all time-batched GEMMs)",
                          "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / PEAK_F32_MFMA_TFLOPS, "traffic": None,
@@ -455,7 +502,6 @@ def main():
                              "algorithmic_bytes": ctc_bytes, "ms": ph["ctc"]},
             "phase_ms": ph,
             "phase_ms_exact_timers": ph_exact,
-            "ms_per_step_median": median_ms,
             "timing_note": "SURVEY 8(d) pipeline: every step's features start in PINNED HOST memory, H2D "
                            "(%.1f MB per step) on a copy stream into one of two device buffers, "
                            "overlapping the previous step's compute, all K uploads inside the timed "
@@ -466,8 +512,7 @@ def main():
             "hbm_resident": {"value": frames_total / elapsed_res, "unit": "frames/s",
                              "ms_per_step": elapsed_res / args.steps * 1e3,
                              "note": "features resident in HBM when the timed region starts"},
-            "cost_mean": float(np.mean(cost[~skip])) if (~skip).any() else None,
-        }
+        })
         out["cost_check"] = oracle_cost_check(cfg, net, host_feats[:T].numpy(), labels[0],
                                               float(cost[0]))
         # ---- side measurements (never `value`): SURVEY 8(d) defines the metric from pinned host

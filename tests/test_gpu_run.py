@@ -148,7 +148,7 @@ def test_bench_two_ranks(backend):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29541" if backend == "gloo" else "29542",
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "6",
-           "--no-side", "--no-cpu-baseline"]
+           "--full", "--no-side", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]
@@ -177,7 +177,7 @@ def test_bench_gpus2_without_a_launcher():
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SCTC_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "6", "--steps", "2", "--warmup", "1",
-           "--no-side", "--no-cpu-baseline"]
+           "--full", "--no-side", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -194,7 +194,7 @@ def test_bench_gpus2_without_a_launcher():
     eff = out["scaling_efficiency_vs_n1"]
     assert eff["n1_ms"] > 0 and eff["n_ms"] > 0 and 0 < eff["value"] < 1.5
     # a failing rank's exit status comes back through the self-launch
-    bad = subprocess.run(cmd[:2] + ["--gpus", "2", "--batch", "0", "--steps", "1", "--warmup", "0", "--no-side",
+    bad = subprocess.run(cmd[:2] + ["--gpus", "2", "--batch", "0", "--steps", "1", "--warmup", "0", "--full", "--no-side",
                                     "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0
 
@@ -210,7 +210,7 @@ def test_bench_four_ranks_gloo_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", "29543",
            os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--batch", "3",
-           "--no-side", "--no-cpu-baseline"]
+           "--full", "--no-side", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -220,6 +220,44 @@ def test_bench_four_ranks_gloo_on_one_gpu():
     assert len(ranks) == 4 and len({r.split(":", 1)[1] for r in ranks}) == 1      # one physical GPU
     assert out["config"]["shared_device_mode"] is True
     assert res.stderr.count("shared=1") == 4                                        # one line per rank
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """bench.py without --full: the headline fields and none of the extra runs; --dump-outputs DIR writes what the last
+    timed step returned (costs, skip flags, every weight gradient, the large ones as a fixed sample) as float32 / float64
+    .npy files under 64 MB, and two runs with the same arguments write the same arrays"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, H, D, NL = 4, 1824, 483, 5
+    outs, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--batch", str(B), "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        outs.append(json.loads(lines[0]))
+        dumps.append({f[:-len(".npy")]: np.load(d / f) for f in sorted(os.listdir(d))})
+    out, dump = outs[0], dumps[0]
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["value"] == pytest.approx(B * 1000 / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    for extra in ("cost_check", "roofline", "phase_ms", "hbm_resident", "pcie_serial", "cfg5_fp16", "cpu_baseline"):
+        assert extra not in out, extra
+    assert set(dump) == ({"cost", "skip", "grad_Wf", "grad_Wb"} |
+                         {"grad_%s%d" % (p, i) for p in "Wb" for i in range(1, NL + 2)})
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in dump.values())
+    assert sum(a.nbytes for a in dump.values()) <= 64 << 20
+    assert dump["cost"].dtype == np.float64 and dump["cost"].shape == (B,) and dump["skip"].shape == (B,)
+    assert dump["grad_W1"].shape == (H, D) and dump["grad_b1"].shape == (H, 1)
+    assert 0 < dump["grad_W2"].size < H * H and np.abs(dump["grad_W2"]).max() > 0
+    live = dump["skip"] == 0
+    assert live.any() and dump["cost"][live].mean() == pytest.approx(out["cost_mean"], rel=1e-12)
+    for name, a in dump.items():
+        np.testing.assert_array_equal(dumps[1][name], a, err_msg=name)
 
 
 @pytest.mark.parametrize("backend", ["gloo", "nccl"])
@@ -300,7 +338,7 @@ def test_bench_single_rank_rccl():
     _require_rccl_one_rank(29564)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-            "--batch", "8", "--no-side", "--no-cpu-baseline"]
+            "--batch", "8", "--full", "--no-side", "--no-cpu-baseline"]
     outs = {}
     for mode in ("single", "dp"):
         env = _rccl_one_rank_env(29562)

@@ -7,7 +7,7 @@ f=$(ls -t $(find gpurun_out/prof_$TAG/stats -name "*kernel_stats.csv") | head -1
 cp gpurun_out/prof_$TAG/pmc_summary.json profiles/${TAG}_pmc_summary.json
 python - <<PY
 import json
-d = json.loads(open('gpurun_out/bench_default.json').read().strip().splitlines()[-1])
+d = json.loads(open('logs/bench_full.json').read().strip().splitlines()[-1])
 json.dump(d, open('profiles/${TAG}_bench.json', 'w'), indent=1)
 print("value %.0f ms %.3f frac %.4f" % (d['value'], d['ms_per_step'], d['roofline']['frac']))
 PY

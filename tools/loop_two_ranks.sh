@@ -11,7 +11,7 @@ pass=0
 for i in $(seq 1 "$N"); do
   t0=$(date +%s%N)
   out=$(python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port $((29600 + i)) bench.py --gpus 2 --steps 2 --warmup 1 --batch 6 --no-side --no-cpu-baseline 2>&1)
+        --master-port $((29600 + i)) bench.py --gpus 2 --steps 2 --warmup 1 --batch 6 --full --no-side --no-cpu-baseline 2>&1)
   rc=$?
   t1=$(date +%s%N)
   line=$(echo "$out" | grep '^{' | tail -1)

@@ -11,10 +11,10 @@ TAG=${1:-r01}
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
 cd $R
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --no-side --no-cpu-baseline > $O/bench_stats.log 2>&1
-timeout 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d $O/pmc_mfma -- python bench.py --steps 2 --warmup 1 --no-side --no-cpu-baseline > $O/bench_pmc_mfma.log 2>&1
-timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python bench.py --steps 2 --warmup 1 --no-side --no-cpu-baseline > $O/bench_pmc_fetch.log 2>&1
-timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python bench.py --steps 2 --warmup 1 --no-side --no-cpu-baseline > $O/bench_pmc_write.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --no-side --no-cpu-baseline > $O/bench_stats.log 2>&1
+timeout 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d $O/pmc_mfma -- python bench.py --steps 2 --warmup 1 --full --no-side --no-cpu-baseline > $O/bench_pmc_mfma.log 2>&1
+timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python bench.py --steps 2 --warmup 1 --full --no-side --no-cpu-baseline > $O/bench_pmc_fetch.log 2>&1
+timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python bench.py --steps 2 --warmup 1 --full --no-side --no-cpu-baseline > $O/bench_pmc_write.log 2>&1
 find $O -name "*.csv" | head -30
 du -sh $O
 tail -2 $O/bench_stats.log | cut -c1-300

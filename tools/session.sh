@@ -18,11 +18,12 @@ for l in sys.stdin:
     f=$(find gpurun_out/prof_ctc -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && grep -i "ctc\|softmax\|Name" $f | cut -c1-200 | head -30
     find gpurun_out/prof_ctc -name "*kernel_trace.csv" -size +5M -delete
     ;;
-bench)    # the headline line without the CPU leg
+bench)    # the headline line with its side measurements, without the CPU leg (bench.py's lines go to logs/)
     shift
-    timeout 900 python bench.py --no-cpu-baseline "$@" > gpurun_out/bench.json 2> gpurun_out/bench.err
-    tail -3 gpurun_out/bench.err
-    python tools/bench_digest.py gpurun_out/bench.json
+    mkdir -p logs
+    timeout 900 python bench.py --full --no-cpu-baseline "$@" > logs/bench.json 2> logs/bench.err
+    tail -3 logs/bench.err
+    python tools/bench_digest.py logs/bench.json
     ;;
 tests)    # pytest -m gpu over the given files / node ids (default: everything)
     shift
@@ -39,8 +40,9 @@ final)    # round-end evidence: full suite, smoke, the rocprofv3 passes of bench
     timeout 1500 bash tools/profile_bench.sh $TAG > gpurun_out/profile_$TAG.log 2>&1
     tail -3 gpurun_out/profile_$TAG.log | cut -c1-200
     cp gpurun_out/prof_$TAG/pmc_summary.json profiles/${TAG}_pmc_summary.json   # bench.py reads the newest summary
-    timeout 1200 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-    python tools/bench_digest.py gpurun_out/bench_default.json
+    mkdir -p logs
+    timeout 1200 python bench.py --full > logs/bench_full.json 2> logs/bench_full.err
+    python tools/bench_digest.py logs/bench_full.json
     ;;
 *)
     echo "usage: tools/session.sh ctc|bench|tests|final [args]"; exit 2;;
