@@ -52,6 +52,8 @@ struct RecArgs {
                             // 47: more than 32 utterances on the one-slab-per-CU kernel of rounds 1-5 (default since round 6 at 1824 / 2048
                             //     units: units x utterances, brnn_recurrent_t_kernel); 50: the tiled kernel at 512 / 1024 units as well
                             //     (no faster there; tests); 49: DIAGNOSTIC, wrong results -- the tiled kernel re-reads step 0's exchange rows
+                            // 51: 17..32 utterances on the two-chain kernel brnn_recurrent_q_kernel (the default up to round 6;
+                            //     since round 7 at 1824 / 2048 units and fp32: the tiled kernel, 16 units x both tiles per CU)
     unsigned* debug;        // nullable: s_memtime stamps [2 wgs][16 steps][8] for steps 64..79
     int32_t b_off;          // rank of this launch's first utterance in the packed minibatch (minibatches of
                             // more than 128 utterances run as several launches; T_b already points at it)

@@ -686,6 +686,12 @@ __global__ __launch_bounds__(256, 2) void brnn_recurrent_q_kernel(RecArgs p)
 // sub-chain (t >> 1) & 1, slot t >> 2: all four chains of a direction get utterances of every length class.
 // NCQ: chunks per wave; NREGF: weight fragments (chunk, unit group) per wave kept in registers; NT: utterance
 // tiles per sub-chain (1: up to 64 utterances, 2: up to 128); NBAT batches per phase, ring of R (NBAT % R == 0).
+// UG = 1 (round 7, 17..32 utterances): 16 units x BOTH utterance tiles of a direction per CU -- grid = 2 directions x
+// H/16 unit blocks (228 at H = 1824, 256 at H = 2048), tile 0 is sub-chain A and tile 1 sub-chain B, one result per
+// phase (wave 0 finishes it, waves 1..3 park their K quarters).  The two-chain kernel gave each tile its own workgroup
+// and put two of them on a CU, in phase: two MFMA bursts back to back, then both chains' fabric round trips with the
+// matrix pipes idle.  Here one tile's round trip runs under the other tile's MFMAs.  Same K split, same MFMAs in the
+// same order, same sums: the rows are those of brnn_recurrent_q_kernel bit for bit.
 template <int... I, class F>
 __device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f)
 {
@@ -697,15 +703,19 @@ __device__ __forceinline__ void static_for(F&& f)
     static_for_seq(std::make_integer_sequence<int, N>(), static_cast<F&&>(f));
 }
 
-template <int NCQ, int NREGF, int NT, int NBAT, int R, int PUB, int PB>
+template <int NCQ, int NREGF, int NT, int NBAT, int R, int PUB, int PB, int UG = 2>
 __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
 {
     extern __shared__ __attribute__((aligned(16))) float4 lds4[];
-    constexpr int NFR = 2 * NCQ;             // weight fragments per wave: f = 2 * chunk + unit group
+    constexpr int NFR = UG * NCQ;            // weight fragments per wave: f = UG * chunk + unit group
     constexpr int NLDSF = NFR - NREGF;       // of them in LDS
     constexpr int XB = (NCQ + NBAT - 1) / NBAT;   // chunks per batch
-    constexpr int NC = 2 * NT;               // results per phase: c = 2 * tile slot + unit group; wave c finishes c
-    static_assert(NC <= 4, "one result per wave");
+    constexpr int NC = UG * NT;              // results per phase: c = UG * tile slot + unit group; wave c finishes c
+    // UG == 1 (17..32 utterances): up to 128 producers per chain, two per polling lane -- producer q's words sit in
+    // slot q % 64 at word (q / 64) * NC, so one 16-byte load of slot `lane` still holds everything a lane checks
+    constexpr int NPL = UG == 1 ? 2 : 1;
+    static_assert(UG == 1 || UG == 2, "16 or 32 units per block");
+    static_assert(NC <= 4 && NPL * NC <= 4, "one result per wave, one 16-byte flag load per lane");
     static_assert(NBAT % R == 0 && NBAT >= 2 * R && R >= 2, "ring");
     static_assert((NBAT - 1) * XB < NCQ, "no empty batch");
     static_assert(PUB >= 0 && PUB + 2 <= PB && PB <= NBAT - R + 1 && PB >= 1,
@@ -713,10 +723,11 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
                   "seen (in front of batch PB), and that before the next phase's first exchange loads (batch NBAT - R + 1)");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int Hp = p.Hp, nch = Hp >> 4, nprod = Hp >> 5;
-    const int combo = blockIdx.x & 3, ublk = blockIdx.x >> 2;
+    const int Hp = p.Hp, nch = Hp >> 4, nprod = nch / UG;
+    // UG == 2: combo = (direction, utterance half), four per grid; UG == 1: combo = direction, both tiles on every CU
+    const int combo = blockIdx.x & (2 * UG - 1), ublk = blockIdx.x / (2 * UG);
     const int g = combo & 1, half = combo >> 1;
-    const int row0 = ublk * 32;
+    const int row0 = ublk * 16 * UG;
     const int uj = lane & 15, kq = lane >> 4;
     const int sync_mode = p.sync_mode;
     const int base = nch >> 2, rem = nch & 3;
@@ -747,8 +758,8 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
     // (a wave whose K quarter has one chunk less than NCQ multiplies that chunk too, with ZERO weights: + 0 exactly, and
     // the MFMA stream has no branch -- a branch around the last chunk's MFMAs cost 0.24 us per phase in waits at its join)
     auto load_w0 = [&](int f) {
-        const float4 w = load_w(c_beg + min(f >> 1, cnt - 1), f & 1);
-        return (f >> 1) < cnt ? w : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 w = load_w(c_beg + min(f / UG, cnt - 1), f % UG);
+        return (f / UG) < cnt ? w : make_float4(0.f, 0.f, 0.f, 0.f);
     };
 #pragma unroll
     for (int f = 0; f < NREGF; ++f) {
@@ -779,14 +790,14 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
         int ub[NT], uT[NT], tile_T[NT];
         unsigned trow[NT];
         int T;                  // steps of this sub-chain (its first tile's first utterance is its longest)
-        unsigned* flags;        // [nprod][REC_FLAG_STRIDE]: words 0..NC-1 of a producer = its finishing waves' step flags
+        unsigned* flags;        // [64][REC_FLAG_STRIDE]: words 0..NC-1 of producer q (+ NC * (q / 64)) = its finishing waves' step flags
         int rb_next[NT];        // rowbase of the next step's frame (fetched one step ahead)
         unsigned xb_next, xb_cur;
     };
     auto init_sub = [&](Sub& S, int sub) {
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            const int tile = (i * 2 + sub) * 2 + half;
+            const int tile = (i * 2 + sub) * UG + half;
             S.trow[i] = (unsigned)tile * 16u;
             S.ub[i] = tile * 16 + uj;
             S.uT[i] = S.ub[i] < p.B ? p.T_b[S.ub[i]] : 0;
@@ -879,6 +890,11 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
         unsigned f = v[0];
 #pragma unroll
         for (int c = 1; c < NC; ++c) f = min(f, v[c]);
+        if constexpr (NPL == 2) {
+            const bool second = lane + 64 < nprod;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) f = second ? min(f, v[NC + c]) : f;
+        }
         return f;
     };
     // every wave for itself: returns once all producers of the chain have published >= target
@@ -1011,7 +1027,7 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
             en.act4 = *reinterpret_cast<const float4*>(act_or_pre + en.out_off);
         };
         // The phase's addresses: exchange offsets of its own later batches, what this wave's epilogue needs (result c = wave:
-        // tile slot c >> 1, unit group c & 1).  Nothing the first MFMAs take (their batch is in flight, the weights are there):
+        // tile slot c / UG, unit group c % UG).  Nothing the first MFMAs take (their batch is in flight, the weights are there):
         // computed BEHIND the first group of four, under the matrix pipe, not in front of it.
         unsigned xin[NT];
         Epi En;
@@ -1028,26 +1044,26 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
         En.lane_active = false;
         En.out_off = 0;
         En.xo = 0;
-        En.xchunk = (unsigned)(2 * ublk + (wave & 1)) * chunk_stride;
-        En.flag = S.flags + ublk * REC_FLAG_STRIDE + wave;
+        En.xchunk = (unsigned)(UG * ublk + wave % UG) * chunk_stride;
+        En.flag = S.flags + (ublk & 63) * REC_FLAG_STRIDE + (ublk >> 6) * NC + wave;
         En.val = (unsigned)(j + 1);
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            if ((wave >> 1) == i && wave < NC) {
+            if (wave / UG == i && wave < NC) {
                 const bool active = j < S.uT[i];
                 const int64_t orow = active ? (int64_t)rb[i] + p.b_off + S.ub[i] : 0;
                 const unsigned xrow = active ? xb_cur + (unsigned)S.ub[i] : 0u;
                 En.xo = xrow * 64u + (unsigned)kq * 16u;
                 if (j < S.tile_T[i]) En.xo = (xb_cur + S.trow[i]) * 64u + (unsigned)lane * 16u;
                 En.lane_active = active;
-                En.out_off = orow * ld + row0 + 16 * (wave & 1) + 4 * kq;
+                En.out_off = orow * ld + row0 + 16 * (wave % UG) + 4 * kq;
             }
         }
         };
         if constexpr (FIRST) { setup(); late_loads(En); }
-        f32x4 acc[2][NT][4];
+        f32x4 acc[UG][NT][4];
 #pragma unroll
-        for (int ug = 0; ug < 2; ++ug)
+        for (int ug = 0; ug < UG; ++ug)
 #pragma unroll
             for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -1060,17 +1076,17 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
         constexpr int WA = 2;
         float4 aq[WA + 1];
         auto prefetch_a = [&](auto G_c) {      // G: group index within the phase = chunk * NC + result
-            constexpr int G = decltype(G_c)::value, cu = G / NC, f = 2 * cu + ((G % NC) & 1);
+            constexpr int G = decltype(G_c)::value, cu = G / NC, f = UG * cu + (G % NC) % UG;
             if constexpr (cu < NCQ && f >= NREGF) aq[G % (WA + 1)] = Wl[(f - NREGF) * 64 + lane];
         };
         // four MFMAs: chunk u of batch bi, result g = 2 * tile slot + unit group
         auto mfma_group = [&](auto bi_c, auto u_c, auto g_c) {
             constexpr int bi = decltype(bi_c)::value, u = decltype(u_c)::value, cu = bi * XB + u;
-            constexpr int gi = decltype(g_c)::value >> 1, ug = decltype(g_c)::value & 1;
+            constexpr int gi = decltype(g_c)::value / UG, ug = decltype(g_c)::value % UG;
             constexpr int G = cu * NC + decltype(g_c)::value;
             prefetch_a(std::integral_constant<int, G + WA>());
             if constexpr (cu < NCQ) {
-                constexpr int f = 2 * cu + ug;
+                constexpr int f = UG * cu + ug;
                 float4 a;
                 if constexpr (f < NREGF) a = wreg[f]; else a = aq[G % (WA + 1)];
                 SCTC_MFMA4(acc[ug][gi], a, x[bi % R][u][gi])
@@ -1102,7 +1118,7 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
             auto park = [&](auto c_c) {
                 constexpr int c = decltype(c_c)::value;
                 float4* rp = red + (size_t)(En.parity * NC * 3) * 64 + lane;
-                const f32x4 s = (acc[c & 1][c >> 1][0] + acc[c & 1][c >> 1][1]) + (acc[c & 1][c >> 1][2] + acc[c & 1][c >> 1][3]);
+                const f32x4 s = (acc[c % UG][c / UG][0] + acc[c % UG][c / UG][1]) + (acc[c % UG][c / UG][2] + acc[c % UG][c / UG][3]);
                 if (wave == c) En.mine = s;
                 else rp[(c * 3 + (wave < c ? wave : wave - 1)) * 64] = make_float4(s[0], s[1], s[2], s[3]);
             };
@@ -2226,6 +2242,36 @@ static int launch_recurrent_one(const RecArgs& a, const LaunchCtx& cx)
         }
     }
 #endif
+    // 17..32 utterances, fp32 operands, H = 1824 / 2048 (round 7): the tiled kernel with 16 units x both utterance tiles of
+    // a direction per CU (UG = 1; 228 / 256 workgroups, one per CU), the tiles' steps alternating.  SCTC_REC_VARIANT=51
+    // keeps the two-chain kernel below (A/B; the same bits).  SCTC_REC_TCFG=1: six batches, ring of three; 3: the weight
+    // slab in LDS instead of the accumulation registers.
+    if (ntiles == 2 && !a.prec16 && (a.variant == 0 || a.variant == 46 || a.variant == 49) && 2 * nwg <= cx.cus) {
+        static const int tcfg = getenv("SCTC_REC_TCFG") ? atoi(getenv("SCTC_REC_TCFG")) : 0;
+        RecKernel tk = nullptr;
+        int nldsf = 0;
+        switch (nwg) {
+            case 114:   // H = 1824
+                tk = tcfg == 1 ? brnn_recurrent_t_kernel<29, 29, 1, 6, 3, 1, 4, 1> : tcfg == 3 ? brnn_recurrent_t_kernel<29, 0, 1, 8, 4, 1, 5, 1>
+                     : brnn_recurrent_t_kernel<29, 29, 1, 8, 4, 1, 5, 1>;
+                nldsf = tcfg == 3 ? 29 : 0;
+                break;
+            case 128:   // H = 2048
+                tk = tcfg == 1 ? brnn_recurrent_t_kernel<32, 32, 1, 6, 3, 1, 4, 1> : tcfg == 3 ? brnn_recurrent_t_kernel<32, 0, 1, 8, 4, 1, 5, 1>
+                     : brnn_recurrent_t_kernel<32, 32, 1, 8, 4, 1, 5, 1>;
+                nldsf = tcfg == 3 ? 32 : 0;
+                break;
+            default: break;
+        }
+        if (tk) {
+            size_t smem = sizeof(float4) * 64 * ((size_t)4 * nldsf + 2 * 3 * 1) + (16 * 8 + 8 * 32) * sizeof(unsigned);
+            // with the slab in registers the kernel would leave room for a second workgroup on a CU: claim more than half
+            // of the 160 KiB so that every workgroup has a CU of its own (the co-residency check counts CUs)
+            smem = std::max(smem, (size_t)81 * 1024);
+            SCTC_TRY(launch_persistent(tk, 2 * nwg, smem, 1, 0, a, cx, &done));
+            if (done) return SCTC_OK;     // otherwise: the two-chain kernel below
+        }
+    }
     if (ntiles == 2 && a.variant != 1 && 4 * nwg <= 2 * cx.cus && (4 * nwg) % 8 == 0) {
         // two chains per CU; NREG keeps the LDS share of the slab at <= 76 KiB per workgroup
         RecKernel qk = nullptr;
