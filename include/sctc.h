@@ -130,6 +130,51 @@ int sctc_softmax_rows(const float* logits_dev, float* probs_dev, int64_t rows, i
 int sctc_argmax_rows(const void* probs_dev, int32_t dtype, int32_t* best_dev, int64_t rows,
                      int32_t A, int64_t ld, void* stream);
 
+/* ---- decoding: ctc_fast/new_decoder/decoder.pyx BeamLMDecoder -----------
+ * Added without an ABI version bump (still 6): sctc_lm_create / sctc_lm_destroy,
+ * sctc_ctc_beam_workspace_bytes, sctc_ctc_beam_decode_batch. */
+
+/* A character n-gram LM on the device (stanford-ctc_amd/arpa_lm.py packs it): an open-addressing
+ * table of `capacity` slots (a power of two, at least one empty), slot of a key = splitmix64(key) &
+ * (capacity-1), then linear probing.  key: the n-gram's word ids (1..255) oldest first, 8 bits each,
+ * newest in the low byte (0 = empty slot); prob / backoff: log10 values.  Order <= 8.  The one
+ * allocating call of the library: the table lives until sctc_lm_destroy. */
+typedef struct sctc_lm* sctc_lm_t;
+int sctc_lm_create(const uint64_t* keys_host, const float* prob_host, const float* backoff_host,
+                   int64_t capacity, int32_t order, int32_t bos_word, sctc_lm_t* out);
+int sctc_lm_destroy(sctc_lm_t lm);
+
+/* BeamLMDecoder.decode(probs, beam, alpha, beta) (decoder.pyx:136-193) for B utterances: CTC prefix
+ * beam search over natural-log probabilities (symbol 0 the blank), rows as in sctc_ctc_batch with
+ * rowbase_dev == NULL (frame t of utterance b = row frame_off[b] + t, T_b[b] >= 0 frames).  The sort
+ * key of a prefix is log(p_nb + p_b) + beta * len, its LM term alpha * log10 P_LM(c | <s> + prefix). */
+typedef struct sctc_beam_config {
+    int32_t B;                 /* utterances */
+    int32_t A;                 /* symbols incl. blank, 2..256 */
+    int32_t dtype;             /* SCTC_F32 | SCTC_F64: type of probs */
+    int32_t beam;              /* 1..256 */
+    int32_t nbest;             /* hypotheses returned per utterance, 1..beam */
+    int32_t reserved;          /* 0 */
+    int64_t ld;                /* row stride of probs in elements (>= A) */
+    const int32_t* T_b;        /* host [B] */
+    const int64_t* frame_off;  /* host [B] */
+    double alpha;              /* LM weight */
+    double beta;               /* length bonus */
+    sctc_lm_t lm;              /* NULL: no LM term */
+    const int32_t* sym_word;   /* host [A]: LM word id (1..255) of symbols 1..A-1; ignored without LM */
+} sctc_beam_config;
+
+/* bytes of device workspace for this batch (0: rejected, sctc_last_error()): per utterance
+ * 24 * beam * A bytes (+ 8 * beam * A with an LM) and 4 * beam bytes per frame */
+size_t sctc_ctc_beam_workspace_bytes(const sctc_beam_config* cfg);
+
+/* Outputs (device): hypothesis n of utterance b (best first) is ids_dev[nbest * sum(T_b[<b]) + n * T_b[b]
+ * + i], i < lengths_dev[b * nbest + n]; scores_dev[b * nbest + n] its sort key (float64).  Fewer than
+ * n + 1 prefixes: length 0, score -inf.  ids_dev holds nbest * sum(T_b) int32. */
+int sctc_ctc_beam_decode_batch(const sctc_beam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                               int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                               size_t workspace_bytes, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

@@ -48,6 +48,14 @@ class Minibatch(ctypes.Structure):
                 ("U_b", c_i32p)]
 
 
+class BeamConfig(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("A", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("beam", ctypes.c_int32), ("nbest", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("ld", ctypes.c_int64), ("T_b", c_i32p), ("frame_off", c_i64p),
+                ("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("lm", vp),
+                ("sym_word", c_i32p)]
+
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -66,6 +74,12 @@ PROTOTYPES = {
                                          vp]),
     "sctc_argmax_rows": (ctypes.c_int, [vp, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32,
                                         ctypes.c_int64, vp]),
+    "sctc_lm_create": (ctypes.c_int, [vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                      ctypes.POINTER(vp)]),
+    "sctc_lm_destroy": (ctypes.c_int, [vp]),
+    "sctc_ctc_beam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BeamConfig)]),
+    "sctc_ctc_beam_decode_batch": (ctypes.c_int, [ctypes.POINTER(BeamConfig), vp, vp, vp, vp, vp,
+                                                  ctypes.c_size_t, vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),

@@ -1,0 +1,619 @@
+// CTC prefix beam search with a character n-gram LM: the reference's BeamLMDecoder.decode
+// (ctc_fast/new_decoder/decoder.pyx:136-193) for a batch of utterances, one workgroup per
+// utterance, every frame of the search inside one launch.  DESIGN.md §4.5 has the semantics
+// and the design points; in short, per frame:
+//   1. cells: beam entry j (rank order) and symbol c form cell j*A + c -- c == 0 is the
+//      prefix itself (blank and repeat terms, plus its parent's extension when the parent is
+//      in the beam), c >= 1 the extension P+c (LM term, plus the "Hold" masses of P+c among
+//      the previous frame's candidates); an extension that IS a beam entry is disabled (its
+//      mass arrives through that entry's own cell), so every prefix is counted once;
+//   2. top-`beam` select: radix select over order-preserving 64-bit keys of the float64
+//      sort key, ties by ascending cell index; then ranks by counting;
+//   3. the new beam: float32 masses, 64-bit prefix hashes, LM context, a back-pointer per
+//      entry and frame (the hypotheses are read back through them at the end);
+//   4. LM rows (log10 P(c | <s> + P) for all c) for the entries that are new; an entry that
+//      carried over keeps its row.
+#include <math.h>
+
+#include <vector>
+
+#include "common.h"
+
+struct sctc_lm {
+    uint64_t* key = nullptr;   // device [cap]; prob / backoff follow in the same allocation
+    float* prob = nullptr;
+    float* bo = nullptr;
+    int64_t cap = 0;
+    int32_t order = 0;
+    int32_t bos = 0;
+    int device = -1;
+};
+
+namespace sctc {
+namespace {
+
+constexpr int NT = 256;       // threads per workgroup
+constexpr int KMAX = 256;     // beam limit
+constexpr int AMAX = 256;     // alphabet limit
+constexpr int HT = 512;       // slots of a beam hash table (load <= 1/2)
+constexpr uint64_t H_EMPTY_PREFIX = 0x6A09E667F3BCC909ull;
+
+struct UttDesc {
+    int64_t frame_off;   // first row of the utterance in probs
+    int64_t ws_off;      // byte offset of its workspace slice
+    int64_t id_off;      // first hypothesis element: ids[nbest * id_off + n * T + i]
+    int32_t T;
+    int32_t pad;
+};
+
+struct BeamArgs {
+    const void* probs;
+    int64_t ld;
+    int32_t f64;
+    int32_t A, K, nbest;
+    double alpha, beta;
+    const UttDesc* utt;
+    const int32_t* sym_word;   // device [A]
+    char* ws;
+    const uint64_t* lm_key;    // nullptr: no LM term
+    const float* lm_prob;
+    const float* lm_bo;
+    uint64_t lm_mask;
+    int32_t lm_order, lm_bos;
+    int32_t* ids;
+    int32_t* lens;
+    double* scores;
+};
+
+// workspace slices are 256-byte aligned on both sides of the launch
+__host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+__host__ __device__ inline uint64_t mix64(uint64_t z)
+{
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+
+// hash of the prefix P+c from the hash of P: a bijection of h for fixed c, and of c for fixed h
+__device__ inline uint64_t hstep(uint64_t h, int c) { return mix64(h ^ ((uint64_t)(c + 1) * 0xD6E8FEB86659FD93ull)); }
+
+// order-preserving map double -> uint64 (larger double, larger key); 0 is never produced
+__device__ inline uint64_t okey(double d)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ inline double okey_inv(uint64_t k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
+}
+
+// max-shifted log(exp a + exp b (+ exp c)); -inf for all -inf (decoder.pyx:32-37 without the shift)
+__device__ inline double lse2(double a, double b)
+{
+    const double m = fmax(a, b);
+    if (m == -INFINITY) return -INFINITY;
+    return m + log(exp(a - m) + exp(b - m));
+}
+__device__ inline double lse3(double a, double b, double c)
+{
+    const double m = fmax(fmax(a, b), c);
+    if (m == -INFINITY) return -INFINITY;
+    return m + log(exp(a - m) + exp(b - m) + exp(c - m));
+}
+
+__device__ inline uint64_t bytes_mask(int m) { return m >= 8 ? ~0ull : ((1ull << (8 * m)) - 1); }
+
+__device__ inline bool lm_find(const BeamArgs& p, uint64_t key, float& pr, float& bo)
+{
+    uint64_t s = mix64(key) & p.lm_mask;
+    while (true) {
+        const uint64_t k = p.lm_key[s];
+        if (k == key) {
+            pr = p.lm_prob[s];
+            bo = p.lm_bo[s];
+            return true;
+        }
+        if (k == 0) return false;
+        s = (s + 1) & p.lm_mask;
+    }
+}
+
+// log10 P(w | ctx): ctx = the last `ctxlen` word ids (newest in the low byte, <s> included);
+// longest n-gram first found by growing the context, then the back-offs of the longer contexts
+// in increasing length, float32 additions in kenlm's order (arpa_lm.ArpaLM.score_ids)
+__device__ float lm_score(const BeamArgs& p, uint64_t ctx, int ctxlen, uint32_t w)
+{
+    float pr = -100.0f, bo = 0.0f;
+    lm_find(p, w, pr, bo);              // every word id the host maps to is a unigram
+    float best = pr;
+    int n = 1;
+    for (int m = 1; m <= ctxlen; ++m) {
+        if (!lm_find(p, ((ctx & bytes_mask(m)) << 8) | w, pr, bo)) break;
+        best = pr;
+        n = m + 1;
+    }
+    for (int m = n; m <= ctxlen; ++m) {
+        if (!lm_find(p, ctx & bytes_mask(m), pr, bo)) break;
+        best = best + bo;
+    }
+    return best;
+}
+
+struct Beam {
+    uint64_t h[KMAX];     // prefix hash
+    uint64_t ph[KMAX];    // hash of the prefix without its last symbol
+    uint64_t ctx[KMAX];   // LM context: last (order-1) word ids of <s> + P
+    double key[KMAX];     // float64 sort key of the cell it came from
+    float pnb[KMAX], pb[KMAX];
+    int32_t last[KMAX];   // last symbol, -1 for the empty prefix
+    int32_t len[KMAX];
+    int32_t prev[KMAX];   // rank in the previous frame's beam when carried over, else -1
+};
+
+struct HTab {
+    uint64_t key[HT];
+    int32_t idx[HT];
+};
+
+__device__ inline int htab_find(const HTab& t, uint64_t h)
+{
+    int s = (int)(h & (HT - 1));
+    while (true) {
+        const int i = t.idx[s];
+        if (i < 0) return -1;
+        if (t.key[s] == h) return i;
+        s = (s + 1) & (HT - 1);
+    }
+}
+
+__device__ inline void htab_insert(HTab& t, uint64_t h, int i)
+{
+    int s = (int)(h & (HT - 1));
+    while (atomicCAS(&t.idx[s], -1, i) != -1) s = (s + 1) & (HT - 1);
+    t.key[s] = h;
+}
+
+// exclusive prefix sum over the workgroup (NT threads, wave64); *total = sum of all
+__device__ int block_excl_scan(int v, int* scratch, int* total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int x = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) scratch[wv] = x;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int i = 0; i < NT / 64; ++i) {
+        const int s = scratch[i];
+        if (i < wv) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + x - v;
+}
+
+__device__ inline double load_prob(const BeamArgs& p, int64_t row, int c)
+{
+    return p.f64 ? ((const double*)p.probs)[row * p.ld + c] : (double)((const float*)p.probs)[row * p.ld + c];
+}
+
+__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
+{
+    __shared__ Beam bm[2];
+    __shared__ HTab tab[2];
+    __shared__ double y[AMAX];
+    __shared__ int32_t par[KMAX];
+    __shared__ uint64_t sel_key[KMAX];
+    __shared__ int32_t sel_idx[KMAX];
+    __shared__ int32_t hist[256];
+    __shared__ int32_t scan_scratch[NT / 64];
+    __shared__ int32_t s_bin, s_above, s_cnt, s_count;
+
+    const int tid = threadIdx.x;
+    const UttDesc u = p.utt[blockIdx.x];
+    const int A = p.A, K = p.K, T = u.T;
+    const int64_t M = (int64_t)K * A;
+    const bool has_lm = p.lm_key != nullptr;
+    const int ctx_max = has_lm ? p.lm_order - 1 : 0;
+    const uint64_t ctx_mask = bytes_mask(ctx_max);
+
+    char* w = p.ws + u.ws_off;
+    float2* cand[2] = {(float2*)w, (float2*)w + M};
+    w += al256(2 * M * sizeof(float2));
+    uint64_t* ckey = (uint64_t*)w;
+    w += al256(M * sizeof(uint64_t));
+    float* rows[2] = {(float*)w, (float*)w + M};
+    if (has_lm) w += al256(2 * M * sizeof(float));
+    int32_t* rec = (int32_t*)w;
+
+    for (int s = tid; s < HT; s += NT) {
+        tab[0].idx[s] = -1;
+        tab[1].idx[s] = -1;
+    }
+    if (tid == 0) {
+        bm[0].h[0] = H_EMPTY_PREFIX;
+        bm[0].ph[0] = 0;
+        bm[0].ctx[0] = has_lm ? ((uint64_t)p.lm_bos & ctx_mask) : 0;
+        bm[0].key[0] = 0.0;
+        bm[0].pnb[0] = -INFINITY;
+        bm[0].pb[0] = 0.0f;
+        bm[0].last[0] = -1;
+        bm[0].len[0] = 0;
+        bm[0].prev[0] = -1;
+    }
+    __syncthreads();
+    if (tid == 0) htab_insert(tab[0], H_EMPTY_PREFIX, 0);
+    if (has_lm)
+        for (int c = tid; c < A; c += NT)
+            rows[0][c] = c == 0 ? 0.0f : lm_score(p, bm[0].ctx[0], ctx_max < 1 ? ctx_max : 1, (uint32_t)p.sym_word[c]);
+    __syncthreads();
+
+    int n = 1, cb = 0, tc = 0, rb = 0;
+    for (int t = 0; t < T; ++t) {
+        const Beam& B = bm[cb];
+        Beam& NB = bm[cb ^ 1];
+        const HTab& cur = tab[tc];
+        const HTab& old = tab[tc ^ 1];
+        const int cw = t & 1, cr = cw ^ 1;
+        const int64_t row = u.frame_off + t;
+        for (int c = tid; c < A; c += NT) y[c] = load_prob(p, row, c);
+        for (int j = tid; j < n; j += NT) par[j] = B.len[j] > 0 ? htab_find(cur, B.ph[j]) : -1;
+        __syncthreads();
+
+        // ---- 1. cells ----------------------------------------------------------------------
+        const int Mn = n * A;
+        const double y0 = y[0];
+        for (int idx = tid; idx < Mn; idx += NT) {
+            const int j = idx / A, c = idx - j * A;
+            const double v0 = (double)B.pnb[j], v1 = (double)B.pb[j];
+            const int l = B.last[j];
+            double nb, bb;
+            int klen;
+            if (c == 0) {
+                nb = -INFINITY;
+                if (B.len[j] > 0) {
+                    const double t0 = v0 + y[l];
+                    const int pj = par[j];
+                    if (pj >= 0) {
+                        const double lmp = has_lm ? p.alpha * (double)rows[rb][pj * A + l] : 0.0;
+                        const double e1 = (double)B.pb[pj] + y[l] + lmp;
+                        const double e0 = B.last[pj] != l ? (double)B.pnb[pj] + y[l] + lmp : -INFINITY;
+                        nb = lse3(t0, e0, e1);
+                    } else {
+                        nb = t0;
+                    }
+                }
+                bb = lse2(v0 + y0, v1 + y0);
+                klen = B.len[j];
+            } else {
+                const uint64_t H = hstep(B.h[j], c);
+                if (htab_find(cur, H) >= 0) {          // P+c is a beam entry: counted there
+                    ckey[idx] = 0;
+                    cand[cw][idx] = make_float2(-INFINITY, -INFINITY);
+                    continue;
+                }
+                const double lmw = has_lm ? p.alpha * (double)rows[rb][idx] : 0.0;
+                const double e1 = v1 + y[c] + lmw;
+                const double e0 = c != l ? v0 + y[c] + lmw : -INFINITY;
+                float2 hv = make_float2(-INFINITY, -INFINITY);
+                const int q = htab_find(old, H);
+                if (q >= 0) hv = cand[cr][(int64_t)q * A];
+                else if (B.prev[j] >= 0) hv = cand[cr][(int64_t)B.prev[j] * A + c];
+                nb = lse3(e0, e1, (double)hv.x + y[c]);
+                bb = lse2((double)hv.x + y0, (double)hv.y + y0);
+                klen = B.len[j] + 1;
+            }
+            const double key = lse2(nb, bb) + p.beta * (double)klen;
+            ckey[idx] = okey(key);
+            cand[cw][idx] = make_float2((float)nb, (float)bb);
+        }
+        __syncthreads();
+
+        // ---- 2. select the K best cells: radix select on the keys ------------------------
+        uint64_t prefix = 0;
+        int need = K, level = 64;
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            for (int idx = tid; idx < Mn; idx += NT) {
+                const uint64_t k = ckey[idx];
+                if (k == 0) continue;
+                if (shift < 56 && (k >> (shift + 8)) != (prefix >> (shift + 8))) continue;
+                atomicAdd(&hist[(k >> shift) & 255], 1);
+            }
+            __syncthreads();
+            const int v = hist[255 - tid];
+            int total;
+            const int above = block_excl_scan(v, scan_scratch, &total);
+            if (shift == 56 && total <= need) break;     // every eligible cell is kept
+            if (above < need && above + v >= need) {
+                s_bin = 255 - tid;
+                s_above = above;
+                s_cnt = v;
+            }
+            __syncthreads();
+            prefix |= (uint64_t)s_bin << shift;
+            need -= s_above;
+            level = shift;
+            const bool done = s_cnt == need;
+            __syncthreads();
+            if (done) break;
+        }
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+        for (int idx = tid; idx < Mn; idx += NT) {
+            const uint64_t k = ckey[idx];
+            if (k == 0) continue;
+            if (level == 64 || (k >> level) > (prefix >> level)) {
+                const int pos = atomicAdd(&s_count, 1);
+                sel_key[pos] = k;
+                sel_idx[pos] = idx;
+            }
+        }
+        __syncthreads();
+        int nsel = s_count;
+        if (level < 64) {
+            // ties with the threshold: the first `need` in cell order
+            const int chunk = (Mn + NT - 1) / NT;
+            const int beg = tid * chunk, end = min(Mn, beg + chunk);
+            int mine = 0;
+            for (int idx = beg; idx < end; ++idx) {
+                const uint64_t k = ckey[idx];
+                mine += (k != 0 && (k >> level) == (prefix >> level));
+            }
+            int total;
+            int rank = block_excl_scan(mine, scan_scratch, &total);
+            for (int idx = beg; idx < end && rank < need; ++idx) {
+                const uint64_t k = ckey[idx];
+                if (k != 0 && (k >> level) == (prefix >> level)) {
+                    sel_key[nsel + rank] = k;
+                    sel_idx[nsel + rank] = idx;
+                    ++rank;
+                }
+            }
+            nsel += need;
+            __syncthreads();
+        }
+
+        // ---- 3. ranks by counting, the new beam --------------------------------------------
+        if (tid < nsel) {
+            const uint64_t k = sel_key[tid];
+            const int ix = sel_idx[tid];
+            int r = 0;
+            for (int i = 0; i < nsel; ++i) {
+                const uint64_t ki = sel_key[i];
+                r += (ki > k) || (ki == k && sel_idx[i] < ix);
+            }
+            const int j = ix / A, c = ix - j * A;
+            const float2 cv = cand[cw][ix];
+            NB.pnb[r] = cv.x;
+            NB.pb[r] = cv.y;
+            NB.key[r] = okey_inv(k);
+            if (c == 0) {
+                NB.h[r] = B.h[j];
+                NB.ph[r] = B.ph[j];
+                NB.ctx[r] = B.ctx[j];
+                NB.last[r] = B.last[j];
+                NB.len[r] = B.len[j];
+                NB.prev[r] = j;
+            } else {
+                NB.h[r] = hstep(B.h[j], c);
+                NB.ph[r] = B.h[j];
+                NB.ctx[r] = has_lm ? (((B.ctx[j] << 8) | (uint64_t)p.sym_word[c]) & ctx_mask) : 0;
+                NB.last[r] = c;
+                NB.len[r] = B.len[j] + 1;
+                NB.prev[r] = -1;
+            }
+            rec[(int64_t)t * K + r] = (j << 16) | c;
+        }
+        // the previous beam's table is no longer needed: it becomes the new beam's
+        HTab& nt = tab[tc ^ 1];
+        for (int s = tid; s < HT; s += NT) nt.idx[s] = -1;
+        __syncthreads();
+        if (tid < nsel) htab_insert(nt, NB.h[tid], tid);
+
+        // ---- 4. LM rows: carried entries keep theirs, new ones query the LM ----------------
+        if (has_lm) {
+            for (int it = tid; it < nsel * A; it += NT) {
+                const int r = it / A, c = it - r * A;
+                const int src = NB.prev[r];
+                float v;
+                if (src >= 0) v = rows[rb][src * A + c];
+                else v = c == 0 ? 0.0f : lm_score(p, NB.ctx[r], min(NB.len[r] + 1, ctx_max), (uint32_t)p.sym_word[c]);
+                rows[rb ^ 1][it] = v;
+            }
+            rb ^= 1;
+        }
+        __syncthreads();
+        n = nsel;
+        cb ^= 1;
+        tc ^= 1;
+    }
+
+    // ---- the n best hypotheses through the back-pointers ----------------------------------
+    const Beam& B = bm[cb];
+    for (int q = tid; q < p.nbest; q += NT) {
+        const int64_t o = (int64_t)blockIdx.x * p.nbest + q;
+        if (q >= n) {
+            p.lens[o] = 0;
+            p.scores[o] = -INFINITY;
+            continue;
+        }
+        const int L = B.len[q];
+        p.lens[o] = L;
+        p.scores[o] = B.key[q];
+        int32_t* out = p.ids + p.nbest * u.id_off + (int64_t)q * T;
+        int r = q, pos = L - 1;
+        for (int t = T - 1; t >= 0 && pos >= 0; --t) {
+            const int e = rec[(int64_t)t * K + r];
+            const int c = e & 0xFFFF;
+            if (c != 0) out[pos--] = c;
+            r = e >> 16;
+        }
+    }
+}
+
+struct BeamPlan {
+    std::vector<UttDesc> utt;
+    size_t head = 0;     // descriptors + symbol map
+    size_t total = 0;
+};
+
+int plan_beam(const sctc_beam_config* cfg, BeamPlan& pl)
+{
+    SCTC_CHECK_ARG(cfg, "beam: null config");
+    SCTC_CHECK_ARG(cfg->B >= 1, "beam: empty batch");
+    SCTC_CHECK_ARG(cfg->A >= 2 && cfg->A <= AMAX, "beam: alphabet size %d outside 2..%d", cfg->A, AMAX);
+    SCTC_CHECK_ARG(cfg->beam >= 1 && cfg->beam <= KMAX, "beam: beam width %d outside 1..%d", cfg->beam, KMAX);
+    SCTC_CHECK_ARG(cfg->nbest >= 1 && cfg->nbest <= cfg->beam, "beam: nbest %d outside 1..beam", cfg->nbest);
+    SCTC_CHECK_ARG(cfg->dtype == SCTC_F32 || cfg->dtype == SCTC_F64, "beam: bad dtype %d", cfg->dtype);
+    SCTC_CHECK_ARG(cfg->ld >= cfg->A, "beam: ld %lld < A %d", (long long)cfg->ld, cfg->A);
+    SCTC_CHECK_ARG(cfg->T_b && cfg->frame_off, "beam: null T_b / frame_off");
+    SCTC_CHECK_ARG(isfinite(cfg->alpha) && isfinite(cfg->beta), "beam: alpha / beta not finite");
+    if (cfg->lm) {
+        SCTC_CHECK_ARG(cfg->sym_word, "beam: an LM needs the symbol -> word map");
+        for (int c = 1; c < cfg->A; ++c)
+            SCTC_CHECK_ARG(cfg->sym_word[c] >= 1 && cfg->sym_word[c] <= 255,
+                           "beam: symbol %d maps to LM word %d outside 1..255", c, cfg->sym_word[c]);
+    }
+    const int64_t M = (int64_t)cfg->beam * cfg->A;
+    const size_t fixed = al256(2 * M * sizeof(float2)) + al256(M * sizeof(uint64_t)) +
+                         (cfg->lm ? al256(2 * M * sizeof(float)) : 0);
+    pl.utt.resize(cfg->B);
+    pl.head = align256(cfg->B * sizeof(UttDesc)) + align256(AMAX * sizeof(int32_t));
+    size_t off = pl.head;
+    int64_t id_off = 0;
+    for (int b = 0; b < cfg->B; ++b) {
+        const int T = cfg->T_b[b];
+        SCTC_CHECK_ARG(T >= 0, "beam: utterance %d has %d frames", b, T);
+        SCTC_CHECK_ARG(cfg->frame_off[b] >= 0, "beam: utterance %d has a negative frame offset", b);
+        UttDesc& d = pl.utt[b];
+        d.frame_off = cfg->frame_off[b];
+        d.ws_off = (int64_t)off;
+        d.id_off = id_off;
+        d.T = T;
+        d.pad = 0;
+        off += fixed + align256((size_t)T * cfg->beam * sizeof(int32_t));
+        id_off += T;
+    }
+    pl.total = off;
+    return SCTC_OK;
+}
+
+}  // namespace
+}  // namespace sctc
+
+using namespace sctc;
+
+extern "C" {
+
+int sctc_lm_create(const uint64_t* keys_host, const float* prob_host, const float* backoff_host,
+                   int64_t capacity, int32_t order, int32_t bos_word, sctc_lm_t* out)
+{
+    SCTC_CHECK_ARG(out && keys_host && prob_host && backoff_host, "lm: null argument");
+    *out = nullptr;
+    SCTC_CHECK_ARG(capacity >= 2 && (capacity & (capacity - 1)) == 0, "lm: capacity %lld not a power of two",
+                   (long long)capacity);
+    SCTC_CHECK_ARG(order >= 1 && order <= 8, "lm: order %d outside 1..8", order);
+    SCTC_CHECK_ARG(bos_word >= 1 && bos_word <= 255, "lm: <s> word id %d outside 1..255", bos_word);
+    int64_t used = 0;
+    for (int64_t i = 0; i < capacity; ++i) used += keys_host[i] != 0;
+    SCTC_CHECK_ARG(used < capacity, "lm: table without an empty slot");
+    int dev = 0;
+    SCTC_HIP_TRY(hipGetDevice(&dev));
+    sctc_lm* lm = new sctc_lm();
+    const size_t kb = capacity * sizeof(uint64_t), fb = capacity * sizeof(float);
+    void* mem = nullptr;
+    hipError_t e = hipMalloc(&mem, kb + 2 * fb);
+    if (e == hipSuccess) e = hipMemcpy(mem, keys_host, kb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char*)mem + kb, prob_host, fb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char*)mem + kb + fb, backoff_host, fb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (mem) (void)hipFree(mem);
+        delete lm;
+        return set_error(SCTC_ERR_HIP, "lm: upload failed: %s", hipGetErrorString(e));
+    }
+    lm->key = (uint64_t*)mem;
+    lm->prob = (float*)((char*)mem + kb);
+    lm->bo = (float*)((char*)mem + kb + fb);
+    lm->cap = capacity;
+    lm->order = order;
+    lm->bos = bos_word;
+    lm->device = dev;
+    *out = lm;
+    return SCTC_OK;
+}
+
+int sctc_lm_destroy(sctc_lm_t lm)
+{
+    if (!lm) return SCTC_OK;
+    if (lm->key) (void)hipFree(lm->key);
+    delete lm;
+    return SCTC_OK;
+}
+
+size_t sctc_ctc_beam_workspace_bytes(const sctc_beam_config* cfg)
+{
+    BeamPlan pl;
+    if (plan_beam(cfg, pl) != SCTC_OK) return 0;
+    return pl.total;
+}
+
+int sctc_ctc_beam_decode_batch(const sctc_beam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                               int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                               size_t workspace_bytes, void* stream)
+{
+    BeamPlan pl;
+    SCTC_TRY(plan_beam(cfg, pl));
+    SCTC_CHECK_ARG(probs_dev && lengths_dev && scores_dev && workspace_dev, "beam: null device pointer");
+    int64_t total_T = 0;
+    for (int b = 0; b < cfg->B; ++b) total_T += cfg->T_b[b];
+    SCTC_CHECK_ARG(ids_dev || total_T == 0, "beam: null ids");
+    if (workspace_bytes < pl.total)
+        return set_error(SCTC_ERR_WORKSPACE, "beam: workspace %zu bytes < %zu needed", workspace_bytes, pl.total);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<char> head(pl.head, 0);
+    memcpy(head.data(), pl.utt.data(), cfg->B * sizeof(UttDesc));
+    const size_t sym_off = align256(cfg->B * sizeof(UttDesc));
+    if (cfg->lm) memcpy(head.data() + sym_off, cfg->sym_word, cfg->A * sizeof(int32_t));
+    // small and synchronous with respect to the host buffer: a plain copy, then the launch
+    SCTC_HIP_TRY(hipMemcpyAsync(workspace_dev, head.data(), pl.head, hipMemcpyHostToDevice, s));
+    SCTC_HIP_TRY(hipStreamSynchronize(s));
+
+    BeamArgs a{};
+    a.probs = probs_dev;
+    a.ld = cfg->ld;
+    a.f64 = cfg->dtype == SCTC_F64;
+    a.A = cfg->A;
+    a.K = cfg->beam;
+    a.nbest = cfg->nbest;
+    a.alpha = cfg->alpha;
+    a.beta = cfg->beta;
+    a.utt = (const UttDesc*)workspace_dev;
+    a.sym_word = (const int32_t*)((char*)workspace_dev + sym_off);
+    a.ws = (char*)workspace_dev;
+    if (cfg->lm) {
+        a.lm_key = cfg->lm->key;
+        a.lm_prob = cfg->lm->prob;
+        a.lm_bo = cfg->lm->bo;
+        a.lm_mask = (uint64_t)(cfg->lm->cap - 1);
+        a.lm_order = cfg->lm->order;
+        a.lm_bos = cfg->lm->bos;
+    }
+    a.ids = ids_dev;
+    a.lens = lengths_dev;
+    a.scores = scores_dev;
+    hipLaunchKernelGGL(ctc_beam_kernel, dim3(cfg->B), dim3(NT), 0, s, a);
+    SCTC_HIP_TRY(hipGetLastError());
+    return SCTC_OK;
+}
+
+}  // extern "C"

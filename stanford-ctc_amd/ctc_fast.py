@@ -10,7 +10,9 @@ libsctc_hip.so.  Same surface, same argument checking, same return values:
 C-contiguous int32 vector, exactly what the Cython memoryview signature accepts;
 anything else raises ``ValueError`` like the memoryview does.  The float64 host
 signature runs the float64 device kernels.  Additional entry points (not in the
-reference) take batches and device tensors: :func:`ctc_loss_batch`.
+reference) take batches and device tensors: :func:`ctc_loss_batch`; and the prefix beam
+search decoder of ``ctc_fast/new_decoder/decoder.pyx`` batched over utterances:
+:func:`decode_beam_batch` with an optional character LM (:class:`DecodeLM`).
 
 There is no CPU fallback: without the HIP library or without a GPU the calls raise.
 """
@@ -171,3 +173,121 @@ def collapse_best_path(best_path, blank=0):
             hyp.append(b)
             align.append(i)
     return hyp, align
+
+
+class DecodeLM(object):
+    """A character n-gram LM on the device for :func:`decode_beam_batch`: an
+    :class:`arpa_lm.ArpaLM` (or the path of an ARPA file) packed and uploaded once, plus
+    the LM word of every CTC symbol -- ``symbols`` is the decoder's ``int_char_map``
+    ({symbol id: token}, chars.txt) or an int32 array of word ids per symbol."""
+
+    def __init__(self, arpa, symbols, A=None):
+        import arpa_lm
+        if not isinstance(arpa, arpa_lm.ArpaLM):
+            arpa = arpa_lm.ArpaLM(arpa)
+        self.arpa = arpa
+        if isinstance(symbols, dict):
+            A = int(A) if A is not None else max(symbols) + 1
+            self.sym_words = arpa.symbol_words(symbols, A)
+        else:
+            self.sym_words = np.ascontiguousarray(symbols, dtype=np.int32)
+        self.handle = None
+        keys, prob, bo = arpa.pack()
+        _sctc.require_gpu()
+        h = ctypes.c_void_p()
+        rc = _sctc.lib().sctc_lm_create(keys.ctypes.data, prob.ctypes.data, bo.ctypes.data, keys.shape[0],
+                                        arpa.order, arpa.bos, ctypes.byref(h))
+        _sctc.check(rc, "DecodeLM")
+        self.handle = h
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            _sctc.lib().sctc_lm_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=None, nbest=1):
+    """CTC prefix beam search with an optional character LM, batched: the
+    reference's ``BeamLMDecoder.decode`` (ctc_fast/new_decoder/decoder.pyx:136-193) for every
+    utterance at once, one workgroup per utterance.
+
+    logprobs: list of (A, T_b) float32/float64 natural-log probability arrays (symbol 0 the
+    blank), or a torch device tensor [sum T][A] with ``lengths`` giving T_b.  lm: a
+    :class:`DecodeLM` or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
+    of int32 symbol-id arrays and float64[B]; with nbest > 1 a list of lists and [B, nbest]
+    (entries beyond the beam: empty, -inf)."""
+    import torch
+    if isinstance(logprobs, torch.Tensor):
+        if lengths is None:
+            raise ValueError("decode_beam_batch: a device tensor needs lengths")
+        if logprobs.dim() != 2:
+            raise ValueError("decode_beam_batch: expected a [sum T][A] tensor")
+        T_b = [int(t) for t in lengths]
+        A = int(logprobs.shape[1])
+        src = logprobs
+        if src.dtype not in (torch.float32, torch.float64):
+            raise ValueError("Buffer dtype mismatch, expected 'double' or 'float'")
+        dtype = _sctc.F64 if src.dtype == torch.float64 else _sctc.F32
+        if sum(T_b) > src.shape[0]:
+            raise ValueError("decode_beam_batch: lengths exceed the tensor's rows")
+    else:
+        arrs = [np.asarray(p) for p in logprobs]
+        if not arrs:
+            raise ValueError("decode_beam_batch: empty batch")
+        for p in arrs:
+            if p.ndim != 2 or p.shape[0] != arrs[0].shape[0]:
+                raise ValueError("decode_beam_batch: every utterance must be an (A, T) array of one A")
+        A = arrs[0].shape[0]
+        T_b = [p.shape[1] for p in arrs]
+        dt = np.float64 if any(p.dtype == np.float64 for p in arrs) else np.float32
+        dtype = _sctc.F64 if dt == np.float64 else _sctc.F32
+        src = None
+    B = len(T_b)
+    if lm is not None and not isinstance(lm, DecodeLM):
+        raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM or None")
+    if lm is not None and lm.sym_words.shape[0] < A:
+        raise ValueError("decode_beam_batch: the LM maps %d symbols, the input has %d"
+                         % (lm.sym_words.shape[0], A))
+    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(T_b)[:-1]]) if B else [], dtype=np.int64)
+    sw = np.ascontiguousarray(lm.sym_words[:A] if lm is not None else np.zeros(A, np.int32), dtype=np.int32)
+    cfg = _sctc.BeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
+                           float(alpha), float(beta), lm.handle if lm is not None else None, _sctc.i32(sw))
+    L = _sctc.lib()
+    nbytes = L.sctc_ctc_beam_workspace_bytes(ctypes.byref(cfg))
+    if nbytes == 0:
+        _sctc.check(-1, "decode_beam_batch")
+    torch = _sctc.require_gpu()
+    if src is None:
+        host = np.concatenate([np.ascontiguousarray(p.T, dtype=dt) for p in arrs], axis=0) if sum(T_b) else \
+            np.zeros((1, A), dtype=dt)
+        dev = torch.from_numpy(host).cuda()
+    else:
+        dev = src.contiguous()
+        cfg.ld = int(dev.stride(0))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev.device)
+    ids = torch.zeros(max(1, nbest * sum(T_b)), dtype=torch.int32, device=dev.device)
+    lens = torch.empty(B * nbest, dtype=torch.int32, device=dev.device)
+    scores = torch.empty(B * nbest, dtype=torch.float64, device=dev.device)
+    rc = L.sctc_ctc_beam_decode_batch(ctypes.byref(cfg), dev.data_ptr(), ids.data_ptr(), lens.data_ptr(),
+                                      scores.data_ptr(), ws.data_ptr(), nbytes, _sctc.current_stream_ptr())
+    _sctc.check(rc, "decode_beam_batch")
+    ids, lens, scores = ids.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy()
+    hyps = []
+    base = 0
+    for b in range(B):
+        row = []
+        for n in range(nbest):
+            o = base + n * T_b[b]
+            row.append(ids[o:o + lens[b * nbest + n]].copy())
+        hyps.append(row)
+        base += nbest * T_b[b]
+    if nbest == 1:
+        return [h[0] for h in hyps], scores
+    return hyps, scores.reshape(B, nbest)

@@ -1,0 +1,122 @@
+"""Drop-in for the reference's Cython module ``ctc_fast/new_decoder/decoder.pyx``:
+the same classes and calls, decoding on the MI355X through libsctc_hip.so.
+
+    DecoderBase.load_chars(charmap_file)                            decoder.pyx:44-59
+    ArgmaxDecoder.decode(probs) -> (hyp, score)                     decoder.pyx:79-100
+    BeamLMDecoder.load_lm(lmfile)                                   decoder.pyx:108-114
+    BeamLMDecoder.decode(probs, beam=40, alpha=1.0, beta=0.0)
+        -> (hyp, score)                                             decoder.pyx:136-193
+
+``probs`` is a float64 (A, T) Fortran-ordered array of natural-log probabilities, as the
+``double[::1,:]`` memoryview accepts; anything else raises like the memoryview does.  The
+LM is an ARPA file read by arpa_lm.py (kenlm is not needed).  ``decode_batch`` (not in
+the reference) decodes a list of utterances in one launch.
+"""
+import numpy as np
+
+import _sctc
+import arpa_lm
+import ctc_fast
+
+
+def _check_probs(probs):
+    if probs is None:
+        raise TypeError("Argument 'probs' must not be None")
+    if not isinstance(probs, np.ndarray):
+        raise TypeError("Argument 'probs' has incorrect type (expected numpy.ndarray)")
+    if probs.ndim != 2:
+        raise ValueError("Buffer has wrong number of dimensions (expected 2, got %d)" % probs.ndim)
+    if probs.dtype != np.float64:
+        raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % probs.dtype)
+    if not probs.flags.f_contiguous:
+        raise ValueError("ndarray is not Fortran contiguous")
+
+
+class DecoderBase(object):
+    def __init__(self):
+        self.char_int_map = None
+        self.int_char_map = None
+
+    def load_chars(self, charmap_file):
+        """``token id`` per line -> char_int_map / int_char_map (decoder.pyx:44-59)"""
+        with open(charmap_file) as fid:
+            self.char_int_map = dict(tuple(l.strip().split()) for l in fid.readlines())
+        self.int_char_map = {}
+        for k, v in list(self.char_int_map.items()):
+            self.char_int_map[k] = int(v)
+            self.int_char_map[int(v)] = k
+        return True
+
+    def decode(self, probs):
+        return None
+
+    def _string(self, ids):
+        return "".join(self.int_char_map[int(i)] for i in ids)
+
+
+class ArgmaxDecoder(DecoderBase):
+    """Per-frame argmax (first maximum wins), collapse repeats, drop blanks; the score is the
+    sum of the argmax log-probabilities.  Unlike ctc_fast.decode_best_path it keeps ids
+    1, 2 and 8 (decoder.pyx:79-100)."""
+
+    def decode(self, probs):
+        _check_probs(probs)
+        torch = _sctc.require_gpu()
+        A, T = probs.shape
+        dev = torch.from_numpy(probs.T).cuda()
+        best = torch.empty(max(T, 1), dtype=torch.int32, device=dev.device)
+        if T:
+            rc = _sctc.lib().sctc_argmax_rows(dev.data_ptr(), _sctc.F64, best.data_ptr(), T, A, A,
+                                              _sctc.current_stream_ptr())
+            _sctc.check(rc, "ArgmaxDecoder.decode")
+        maxInd = best.cpu().numpy()[:T]
+        hyp = []
+        hyp_score = 0.0
+        pmInd = -1
+        for t in range(T):
+            hyp_score = hyp_score + probs[maxInd[t], t]
+            if maxInd[t] != pmInd:
+                pmInd = maxInd[t]
+                if pmInd > 0:
+                    hyp.append(self.int_char_map[int(pmInd)])
+        return "".join(hyp), hyp_score
+
+
+class BeamLMDecoder(DecoderBase):
+    """Prefix beam search with a character LM (decoder.pyx:103-193), DESIGN.md §4.5."""
+
+    def __init__(self):
+        DecoderBase.__init__(self)
+        self.lm = None
+        self._dev = {}
+
+    def load_lm(self, lmfile):
+        self.lm = arpa_lm.ArpaLM(lmfile)
+        self._dev = {}
+        return True
+
+    def _device_lm(self, A):
+        if self.lm is None:
+            raise ValueError("BeamLMDecoder: load_lm first")
+        if self.int_char_map is None:
+            raise ValueError("BeamLMDecoder: load_chars first")
+        if A not in self._dev:
+            self._dev[A] = ctc_fast.DecodeLM(self.lm, self.int_char_map, A)
+        return self._dev[A]
+
+    def decode(self, probs, beam=40, alpha=1.0, beta=0.0):
+        _check_probs(probs)
+        (hyp, score), = self.decode_batch([probs], beam, alpha, beta)
+        return hyp, score
+
+    def decode_batch(self, probs_list, beam=40, alpha=1.0, beta=0.0):
+        """[(hyp, score)] for a list of (A, T) log-probability arrays, one launch"""
+        if int(beam) < 0:
+            raise OverflowError("can't convert negative value to unsigned int")
+        for p in probs_list:
+            if not isinstance(p, np.ndarray) or p.ndim != 2:
+                raise ValueError("decode_batch: (A, T) arrays expected")
+        A = probs_list[0].shape[0]
+        ids, scores = ctc_fast.decode_beam_batch(probs_list, beam=beam, alpha=alpha, beta=beta,
+                                                 lm=self._device_lm(A))
+        return [(self._string(h), float(s)) for h, s in zip(ids, scores)]
