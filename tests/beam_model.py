@@ -2,7 +2,12 @@
 ``BeamLMDecoder.decode``, ctc_fast/new_decoder/decoder.pyx:136-193), written the way the
 device kernel works: float32 beam state between frames, float64 accumulation, the
 max-shifted combine, candidates ordered by (key descending, cell index ascending) with cell
-index = beam rank * A + symbol (0 = the prefix itself).  The yardstick of the GPU tests."""
+index = beam rank * A + symbol (0 = the prefix itself).  The yardstick of the GPU tests.
+
+alpha * LM is a float64 product, as in the reference (Python floats) and in the kernel
+(``p.alpha * (double)row``): ``alpha * row[c]`` with a NumPy float32 scalar would be multiplied
+and rounded in float32 (NumPy 2 keeps the array scalar's type), invisible only while alpha is
+a float32 number."""
 import math
 
 import numpy as np
@@ -21,9 +26,18 @@ def f32(x):
     return float(np.float32(x))
 
 
-def decode(probs, beam=40, alpha=1.0, beta=0.0, lm_row=None, nbest=1):
+BEAM_CELL, EXT_CELL = 0, 1         # trace "kinds": the cell of a beam entry / of an extension
+
+
+def decode(probs, beam=40, alpha=1.0, beta=0.0, lm_row=None, nbest=1, trace=None):
     """probs: (A, T) natural-log probabilities.  lm_row(prefix tuple) -> A log10 values
-    (None: no LM term).  Returns [(prefix tuple, score)] of the best ``nbest``."""
+    (None: no LM term).  Returns [(prefix tuple, score)] of the best ``nbest``.
+
+    trace: a list that receives one dict per frame: ``beam`` the whole new beam in rank order
+    as (prefix, key); ``kinds`` the kind of cell each entry came from (BEAM_CELL: the prefix
+    was a beam entry, EXT_CELL: an extension; the two sum their terms in different orders);
+    ``cut`` / ``cut_kind`` / ``cut_prefix`` the key, kind and prefix of the best candidate that
+    was not kept (None when every candidate was kept)."""
     probs = np.asarray(probs, dtype=np.float64)
     A, T = probs.shape
     # beam: list of (prefix, p_nb f32, p_b f32, key f64), best first
@@ -40,7 +54,7 @@ def decode(probs, beam=40, alpha=1.0, beta=0.0, lm_row=None, nbest=1):
             if P and P[:-1] in idx:
                 pj = idx[P[:-1]]
                 _, w0, w1, _ = cur[pj]
-                lm = alpha * rows[P[:-1]][l] if lm_row is not None else 0.0
+                lm = alpha * float(rows[P[:-1]][l]) if lm_row is not None else 0.0
                 if len(P) == 1 or P[-2] != l:
                     nb.append(w0 + y[l] + lm)
                 nb.append(w1 + y[l] + lm)
@@ -51,7 +65,7 @@ def decode(probs, beam=40, alpha=1.0, beta=0.0, lm_row=None, nbest=1):
                 Q = P + (c,)
                 if Q in idx:
                     continue
-                lm = alpha * rows[P][c] if lm_row is not None else 0.0
+                lm = alpha * float(rows[P][c]) if lm_row is not None else 0.0
                 nb = [v1 + y[c] + lm]
                 if c != l:
                     nb.append(v0 + y[c] + lm)
@@ -63,6 +77,14 @@ def decode(probs, beam=40, alpha=1.0, beta=0.0, lm_row=None, nbest=1):
         hold = {P: (f32(nbv), f32(bv)) for _, _, P, nbv, bv in cells}
         cells.sort(key=lambda e: (-e[0], e[1]))
         cur = [(P, f32(nbv), f32(bv), key) for key, _, P, nbv, bv in cells[:beam]]
+        if trace is not None:
+            kind = lambda e: BEAM_CELL if e[1] % A == 0 else EXT_CELL
+            cut = cells[beam] if len(cells) > beam else None
+            trace.append({"beam": [(e[2], e[0]) for e in cells[:beam]],
+                          "kinds": [kind(e) for e in cells[:beam]],
+                          "cut": cut[0] if cut else None,
+                          "cut_kind": kind(cut) if cut else None,
+                          "cut_prefix": cut[2] if cut else None})
         if lm_row is not None:
             rows = {P: (rows[P] if P in rows else np.asarray(lm_row(P), dtype=np.float32))
                     for P, _, _, _ in cur}

@@ -24,8 +24,21 @@ Fixtures written:
                                     (from tests/beam_model.py: the reference returns only the
                                     top entry); hypotheses are compared only where the margin
                                     is >= 1e-6, scores always
+  decode_ref_trace.npz              a second case list (TRACE_CASES) with alpha and beta that are
+                                    not float32 numbers: per case the inputs and, for EVERY
+                                    truncation lp[:, :t], t = 1..T, the reference's hypothesis
+                                    (symbol ids, concatenated; ``len`` splits them) and score --
+                                    the reference's top entry after every frame
+
+The two case lists draw from generators of their own, so decode_ref.npz does not depend on the
+second list.  The committed decode_ref.npz predates the float64 alpha * LM product of
+tests/beam_model.py: a regenerated file has every array of the reference equal (lp, cfg, hyp, score)
+and the model-derived ``margin`` of the six alpha = 1.5 cases moved by at most 6e-8, far from the
+1e-6 they are compared with, so the committed file was left as it is.  --out DIR writes
+everything elsewhere (to compare with the committed files).
 
 Usage:  python tests/golden/make_golden_decode.py --reference <reference checkout> [--scratch DIR]
+                                                  [--out DIR]
 """
 import argparse
 import collections as _collections
@@ -271,49 +284,96 @@ CASES = [   # (A, T, beam, alpha, beta, lm, kind)
 ]
 
 
+TRACE_CASES = [   # (A, T, beam, alpha, beta, lm, kind): every truncation is decoded
+    (35, 40, 40, 0.8, 0.37, "5g", "peaked"),
+    (35, 40, 16, 1.3, 0.0, "2g", "peaked"),
+    (8, 40, 40, 1.3, 0.0, "5g", "flat"),
+    (8, 40, 16, 0.8, 0.37, "2g", "peaked"),
+    (35, 36, 16, 1.3, 0.37, "5g", "missing"),
+    (35, 30, 40, 0.8, 0.0, "2g", "missing"),
+]
+
+
+def split_ids(hyp, int_char, A):
+    """the reference's string back to symbol ids (tokens are distinct, at most one per symbol;
+    '[...]' tokens are multi-character, so match greedily against the map)"""
+    ids = []
+    pos = 0
+    by_len = sorted(int_char.items(), key=lambda kv: -len(kv[1]))
+    while pos < len(hyp):
+        for s, tok in by_len:
+            if hyp.startswith(tok, pos) and s < A:
+                ids.append(s)
+                pos += len(tok)
+                break
+        else:
+            raise AssertionError("cannot split %r" % hyp)
+    return ids
+
+
+def trace_cases(dec, chars, out_dir, int_char):
+    rs = np.random.RandomState(4202)
+    out = {"n": np.int64(len(TRACE_CASES))}
+    for i, (A, T, beam, alpha, beta, lmk, kind) in enumerate(TRACE_CASES):
+        assert float(np.float32(alpha)) != alpha
+        d = dec.BeamLMDecoder()
+        d.load_chars(chars)
+        d.load_lm(os.path.join(out_dir, "lm_char_%s.arpa" % lmk))
+        lp = posteriors(rs, A, T, kind)
+        t0 = time.time()
+        ids, lens, scores = [], [], []
+        for t in range(1, T + 1):
+            hyp, score = d.decode(np.asfortranarray(lp[:, :t]), beam, alpha, beta)
+            h = split_ids(hyp, int_char, A)
+            ids += h
+            lens.append(len(h))
+            scores.append(score)
+        print("trace case %d A=%2d T=%2d beam=%2d alpha=%.2f beta=%.2f %s %-7s final score %.6f %.1fs"
+              % (i, A, T, beam, alpha, beta, lmk, kind, scores[-1], time.time() - t0))
+        out["lp%d" % i] = lp
+        out["cfg%d" % i] = np.array([A, T, beam, alpha, beta], dtype=np.float64)
+        out["lm%d" % i] = np.array(lmk)
+        out["kind%d" % i] = np.array(kind)
+        out["hyp%d" % i] = np.array(ids, dtype=np.int32)
+        out["len%d" % i] = np.array(lens, dtype=np.int32)
+        out["score%d" % i] = np.array(scores, dtype=np.float64)
+    np.savez_compressed(os.path.join(out_dir, "decode_ref_trace.npz"), **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True, help="checkout of the reference project")
     ap.add_argument("--scratch", default="/tmp/sctc_ref_decoder")
+    ap.add_argument("--out", default=HERE, help="where the fixtures are written")
     a = ap.parse_args()
     assert not os.path.abspath(a.scratch).startswith(ROOT), "scratch must be outside the repo"
+    OUT = os.path.abspath(a.out)
+    os.makedirs(OUT, exist_ok=True)
     rs = np.random.RandomState(2024)
     sents = corpus(rs)
     lm_text = {"2g": build_arpa(sents, 2, 1, with_unk=False),
                "5g": build_arpa(sents, 5, 2, with_unk=True)}
     for k, txt in lm_text.items():
-        with open(os.path.join(HERE, "lm_char_%s.arpa" % k), "w") as f:
+        with open(os.path.join(OUT, "lm_char_%s.arpa" % k), "w") as f:
             f.write(txt)
-    chars = os.path.join(HERE, "chars.txt")
+    chars = os.path.join(OUT, "chars.txt")
     with open(chars, "w") as f:
         for i, t in enumerate(TOKENS):
             f.write("%s %d\n" % (t, i + 1))
     dec = build_reference(a.reference, a.scratch)
-    lms = {k: arpa_lm.ArpaLM(os.path.join(HERE, "lm_char_%s.arpa" % k)) for k in lm_text}
+    lms = {k: arpa_lm.ArpaLM(os.path.join(OUT, "lm_char_%s.arpa" % k)) for k in lm_text}
     int_char = {i + 1: t for i, t in enumerate(TOKENS)}
     out = {"n": np.int64(len(CASES))}
     with np.errstate(all="ignore"):
         for i, (A, T, beam, alpha, beta, lmk, kind) in enumerate(CASES):
             d = dec.BeamLMDecoder()
             d.load_chars(chars)
-            d.load_lm(os.path.join(HERE, "lm_char_%s.arpa" % lmk))
+            d.load_lm(os.path.join(OUT, "lm_char_%s.arpa" % lmk))
             lp = np.asfortranarray(posteriors(rs, A, T, kind))
             t0 = time.time()
             hyp, score = d.decode(lp, beam, alpha, beta)
             dt = time.time() - t0
-            # the reference's string back to symbol ids (tokens are distinct, at most one per
-            # symbol; '[...]' tokens are multi-character, so match greedily against the map)
-            ids = []
-            pos = 0
-            by_len = sorted(int_char.items(), key=lambda kv: -len(kv[1]))
-            while pos < len(hyp):
-                for s, tok in by_len:
-                    if hyp.startswith(tok, pos) and s < A:
-                        ids.append(s)
-                        pos += len(tok)
-                        break
-                else:
-                    raise AssertionError("cannot split %r" % hyp)
+            ids = split_ids(hyp, int_char, A)
             sw = lms[lmk].symbol_words(int_char, A)
             top2 = beam_model.decode(lp, beam, alpha, beta, beam_model.arpa_rows(lms[lmk], sw), nbest=2)
             margin = top2[0][1] - top2[1][1] if len(top2) > 1 else np.inf
@@ -330,7 +390,8 @@ def main():
             out["hyps%d" % i] = np.array(hyp)
             out["score%d" % i] = np.float64(score)
             out["margin%d" % i] = np.float64(margin)
-    np.savez_compressed(os.path.join(HERE, "decode_ref.npz"), **out)
+        np.savez_compressed(os.path.join(OUT, "decode_ref.npz"), **out)
+        trace_cases(dec, chars, OUT, int_char)
 
 
 if __name__ == "__main__":

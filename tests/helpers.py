@@ -214,3 +214,35 @@ def oracle_variants(params, data, lab, TL, jobs, max_act=20.0):
             return pool.map(_oracle_variant, range(len(jobs)), chunksize=1)
     finally:
         _VARIANT_CTX = None
+
+
+def arpa_backoff(lm, ctx, w):
+    """textbook back-off in float64 over ``ArpaLM.ngrams``: p(w|h) if listed, else
+    bo(h) + p(w|h minus its oldest word)"""
+    ng = lm.ngrams
+    h = tuple(ctx)[-(lm.order - 1):] if lm.order > 1 else ()
+    total = 0.0
+    while True:
+        if h + (w,) in ng:
+            return total + float(ng[h + (w,)][0])
+        if not h:
+            raise AssertionError("no unigram")
+        total += float(ng[h][1]) if h in ng else 0.0
+        h = h[1:]
+
+
+def arpa_backoff_terms(lm, ctx, w):
+    """the same walk, term by term: (length of the longest listed n-gram, [its log10 prob, then
+    the back-offs of the longer contexts, shortest context first]) -- the order in which a
+    float32 scorer adds them; contexts that are not listed contribute nothing"""
+    ng = lm.ngrams
+    h = tuple(ctx)[-(lm.order - 1):] if lm.order > 1 else ()
+    bos = []
+    while True:
+        if h + (w,) in ng:
+            return len(h) + 1, [float(ng[h + (w,)][0])] + bos[::-1]
+        if not h:
+            raise AssertionError("no unigram")
+        if h in ng:
+            bos.append(float(ng[h][1]))
+        h = h[1:]

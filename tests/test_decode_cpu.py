@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import beam_model
+from tests.helpers import arpa_backoff as brute
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -41,20 +42,6 @@ ngram 3=2
 
 \\end\\
 """
-
-
-def brute(lm, ctx, w):
-    """textbook back-off in float64: p(w|h) if listed, else bo(h) + p(w|h minus its oldest word)"""
-    ng = lm.ngrams
-    h = tuple(ctx)[-(lm.order - 1):] if lm.order > 1 else ()
-    total = 0.0
-    while True:
-        if h + (w,) in ng:
-            return total + float(ng[h + (w,)][0])
-        if not h:
-            raise AssertionError("no unigram")
-        total += float(ng[h][1]) if h in ng else 0.0
-        h = h[1:]
 
 
 def check_lm(lm, rs, n=300):
@@ -188,6 +175,90 @@ def test_restatement_against_reference():
             assert list(hyp) == list(z["hyp%d" % i]), i
         compared += 1
     assert compared >= 25
+
+
+def test_restatement_against_reference_truncations():
+    """the reference's top entry after EVERY frame (decode_ref_trace.npz: each truncation lp[:, :t]
+    decoded by the reference), at alpha / beta that are no float32 numbers, against the model's
+    trace.  alpha is handed over as a Python float, as callers do: a model that multiplied
+    alpha * LM in float32 misses the 1e-9 here (1.2e-7 relative at alpha 0.8 and 1.3)."""
+    import arpa_lm
+    z = np.load(os.path.join(GOLDEN, "decode_ref_trace.npz"))
+    lms = {k: arpa_lm.ArpaLM(os.path.join(GOLDEN, "lm_char_%s.arpa" % k)) for k in ("2g", "5g")}
+    frames = compared = 0
+    seen = set()
+    for i in range(int(z["n"])):
+        A, T, beam = (int(v) for v in z["cfg%d" % i][:3])
+        alpha, beta = float(z["cfg%d" % i][3]), float(z["cfg%d" % i][4])
+        assert float(np.float32(alpha)) != alpha
+        seen.add((A, beam, str(z["lm%d" % i])))
+        lm = lms[str(z["lm%d" % i])]
+        trace = []
+        top = beam_model.decode(z["lp%d" % i], beam, alpha, beta, beam_model.arpa_rows(lm, sym_words(lm, A)),
+                                trace=trace)
+        assert len(trace) == T and top[0] == trace[-1]["beam"][0]
+        ends = np.cumsum(z["len%d" % i])
+        for t, fr in enumerate(trace):
+            (hyp, score), ref = fr["beam"][0], float(z["score%d" % i][t])
+            assert abs(score - ref) <= 1e-9 * abs(ref) + 1e-12, (i, t, alpha, score, ref)
+            if len(fr["beam"]) < 2 or score - fr["beam"][1][1] >= 1e-6:
+                assert list(hyp) == list(z["hyp%d" % i][ends[t] - z["len%d" % i][t]:ends[t]]), (i, t)
+                compared += 1
+            frames += 1
+    assert frames >= 200 and compared >= 0.9 * frames
+    assert {a for a, _, _ in seen} == {8, 35} and {b for _, b, _ in seen} == {16, 40}
+    assert os.path.getsize(os.path.join(GOLDEN, "decode_ref_trace.npz")) < 200 * 1024
+
+
+def test_trace_option_leaves_results_alone():
+    rs = np.random.RandomState(3)
+    lp = np.log(rs.dirichlet(np.ones(6), size=12).T)
+    plain = beam_model.decode(lp, 5, 0.0, 0.4, None, nbest=5)
+    trace = []
+    assert beam_model.decode(lp, 5, 0.0, 0.4, None, nbest=5, trace=trace) == plain
+    assert [e for e in trace[-1]["beam"]] == plain and len(trace) == 12
+    assert trace[0]["cut"] is not None and trace[0]["cut"] <= trace[0]["beam"][-1][1]
+    assert beam_model.decode(lp[:, :1], 8, 0.0, 0.4, None, trace=trace) and trace[-1]["cut"] is None
+    for t in range(1, 12):                     # the beam after frame t is the final beam of lp[:, :t]
+        assert beam_model.decode(lp[:, :t], 5, 0.0, 0.4, None, nbest=5) == trace[t - 1]["beam"]
+
+
+def test_lm_row_read_off_on_the_model():
+    """the read-off of tests/test_gpu_decode_trace.py, applied to the model: forced prefixes give
+    back the float32 rows, which lie within the float32 summation bound of a float64 back-off"""
+    import arpa_lm
+    from tests import beam_trace as bt
+    lm = arpa_lm.ArpaLM(os.path.join(GOLDEN, "lm_char_5g.arpa"))
+    sw = sym_words(lm, 35)
+    rs = np.random.RandomState(31)
+    prefixes = bt.lm_row_prefixes(lm, sw, rs)[::3]
+    rows = []
+    for P in prefixes:
+        lp = bt.forced_prefix_frames(rs, 35, P)
+        res = beam_model.decode(lp, 40, 0.7, 0.0, beam_model.arpa_rows(lm, sw), nbest=40)
+        rows.append(bt.recover_lm_row(P, lp, [r[0] for r in res], [r[1] for r in res], 0.7))
+    st = bt.check_lm_rows(lm, sw, prefixes, rows, 0.7)
+    assert st["pairs"] >= 200 and st["early_break"] and st["full_chain"] and st["single"] >= 20
+
+
+def test_tie_inputs_hold_their_preconditions():
+    """the cheap inputs of the GPU tie tests: the model cuts inside a -inf tie / an exact tie of
+    one cell kind often enough, and relies on no tie across cell kinds"""
+    from tests import beam_trace as bt
+    lp = bt.sparse_frames(np.random.RandomState(2000), 8, 40)
+    st = bt.check_model(bt.model_trace(lp, 32, 0.0, 0.4, None), 32, near_cap=0.0)
+    assert 2 * st["cut_in_inf_tie"] >= 40
+    lp = bt.dead_frame(np.random.RandomState(2101), 8, 40, 12)
+    st = bt.check_model(bt.model_trace(lp, 32, 0.0, 0.4, None), 32, near_cap=0.0)
+    assert 2 * st["cut_in_inf_tie"] >= 40
+    for seed in (0, 2, 4, 7):
+        lp = bt.twins(np.random.RandomState(2200 + seed), 7, 40, [(1, 2), (4, 6)])
+        st = bt.check_model(bt.model_trace(lp, 12, 0.0, 0.3, None), 12, exact_ties=True)
+        assert st["ties"] >= 300 and st["cut_in_tie"] >= 5
+    # and a seed whose ties cross cell kinds is refused
+    lp = bt.twins(np.random.RandomState(2203), 7, 40, [(1, 2), (4, 6)])
+    with pytest.raises(AssertionError):
+        bt.check_model(bt.model_trace(lp, 12, 0.0, 0.3, None), 12, exact_ties=True)
 
 
 def test_restatement_edges():
