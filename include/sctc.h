@@ -175,6 +175,60 @@ int sctc_ctc_beam_decode_batch(const sctc_beam_config* cfg, const void* probs_de
                                int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
                                size_t workspace_bytes, void* stream);
 
+/* ---- decoding to words: ctc_fast/decoder/bg_decoder.pyx decode_bg_lm -----
+ * Added without an ABI version bump (still 6): sctc_lexicon_create / sctc_lexicon_destroy /
+ * sctc_lexicon_bytes, sctc_ctc_lexbeam_workspace_bytes, sctc_ctc_lexbeam_decode_batch. */
+
+/* A lexicon on the device (stanford-ctc_amd/decoder/prefixTree.py flattens it): the prefix tree of
+ * the word list and the word-bigram LM of fastdecode/lm.cpp.
+ *   child_host [nodes * A]  child node of (node, symbol) or -1; node 0 is the root; no node has a
+ *                           child for the blank or for `space`, no child is the root
+ *   word_host  [nodes]      id of the word that ends at the node or -1; the root is no word
+ *   ug_prob_host / ug_backoff_host [n_words]  natural-log unigram value and back-off
+ *   bg_keys_host / bg_vals_host [bg_capacity] open addressing, capacity a power of two with at least
+ *                           one empty slot: key (w1 << 32) | w2, all ones = empty, slot of a key =
+ *                           splitmix64(key) & (capacity-1), then linear probing
+ * bg_prob(w1, w2) is the listed value unless that is missing or exactly 0, then the float32 sum
+ * ug_backoff[w1] + ug_prob[w2] (lm.cpp:119-127).  start_word: the id of <s>.  Allocates; the
+ * lexicon lives until sctc_lexicon_destroy.  Every index the search follows is checked here. */
+typedef struct sctc_lexicon* sctc_lexicon_t;
+int sctc_lexicon_create(const int32_t* child_host, const int32_t* word_host, int64_t nodes, int32_t A,
+                        int32_t space, const float* ug_prob_host, const float* ug_backoff_host, int64_t n_words,
+                        const uint64_t* bg_keys_host, const float* bg_vals_host, int64_t bg_capacity,
+                        int32_t start_word, sctc_lexicon_t* out);
+int sctc_lexicon_destroy(sctc_lexicon_t lexicon);
+/* bytes of device memory the lexicon holds (0 for NULL) */
+size_t sctc_lexicon_bytes(sctc_lexicon_t lexicon);
+
+/* decode_bg_lm(probs, prefixTree, lm, beam, alpha, beta) for B utterances: the prefix beam search of
+ * sctc_ctc_beam_decode_batch in which a prefix may only spell lexicon words separated by `space`, the
+ * LM term is alpha * bg_prob(previous word, word) when the space after a word is emitted, and the sort
+ * key is log(p_nb + p_b) + beta * (words finished). */
+typedef struct sctc_lexbeam_config {
+    int32_t B;                 /* utterances */
+    int32_t A;                 /* symbols incl. blank: the A the lexicon was created with */
+    int32_t dtype;             /* SCTC_F32 | SCTC_F64: type of probs */
+    int32_t beam;              /* 1..256 */
+    int32_t nbest;             /* hypotheses returned per utterance, 1..beam */
+    int32_t space;             /* the word separator symbol, 1..A-1 */
+    int64_t ld;                /* row stride of probs in elements (>= A) */
+    const int32_t* T_b;        /* host [B] */
+    const int64_t* frame_off;  /* host [B] */
+    double alpha;              /* LM weight */
+    double beta;               /* word bonus */
+    sctc_lexicon_t lexicon;
+} sctc_lexbeam_config;
+
+/* bytes of device workspace (0: rejected, sctc_last_error()): per utterance 24 * beam * A bytes and
+ * 4 * beam bytes per frame */
+size_t sctc_ctc_lexbeam_workspace_bytes(const sctc_lexbeam_config* cfg);
+
+/* Outputs as sctc_ctc_beam_decode_batch writes them.  After a cut the beam may hold fewer than
+ * `beam` prefixes (few words fit): ranks beyond them report length 0 and score -inf. */
+int sctc_ctc_lexbeam_decode_batch(const sctc_lexbeam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                                  int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                                  size_t workspace_bytes, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

@@ -56,6 +56,13 @@ class BeamConfig(ctypes.Structure):
                 ("sym_word", c_i32p)]
 
 
+class LexBeamConfig(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("A", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("beam", ctypes.c_int32), ("nbest", ctypes.c_int32), ("space", ctypes.c_int32),
+                ("ld", ctypes.c_int64), ("T_b", c_i32p), ("frame_off", c_i64p),
+                ("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("lexicon", vp)]
+
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -80,6 +87,14 @@ PROTOTYPES = {
     "sctc_ctc_beam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BeamConfig)]),
     "sctc_ctc_beam_decode_batch": (ctypes.c_int, [ctypes.POINTER(BeamConfig), vp, vp, vp, vp, vp,
                                                   ctypes.c_size_t, vp]),
+    "sctc_lexicon_create": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, vp,
+                                           ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_int32,
+                                           ctypes.POINTER(vp)]),
+    "sctc_lexicon_destroy": (ctypes.c_int, [vp]),
+    "sctc_lexicon_bytes": (ctypes.c_size_t, [vp]),
+    "sctc_ctc_lexbeam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(LexBeamConfig)]),
+    "sctc_ctc_lexbeam_decode_batch": (ctypes.c_int, [ctypes.POINTER(LexBeamConfig), vp, vp, vp, vp, vp,
+                                                     ctypes.c_size_t, vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),

@@ -13,6 +13,12 @@
 //      entry and frame (the hypotheses are read back through them at the end);
 //   4. LM rows (log10 P(c | <s> + P) for all c) for the entries that are new; an entry that
 //      carried over keeps its row.
+//
+// The same body, instantiated a second time (LEX), is the lexicon-constrained word-bigram search
+// (the reference's ctc_fast/decoder/bg_decoder.pyx:18-95): every beam entry also
+// carries its prefix-tree node, the previous word, the word count and the cached bigram term of
+// its space extension; an extension the tree forbids is no candidate, the LM term is the word
+// bigram at a space, and the length bonus counts words.
 #include <math.h>
 
 #include <vector>
@@ -26,6 +32,22 @@ struct sctc_lm {
     int64_t cap = 0;
     int32_t order = 0;
     int32_t bos = 0;
+    int device = -1;
+};
+
+// The device lexicon of the word-bigram search: the flattened prefix tree (dense child table,
+// word id per node), the unigram arrays and an open-addressing table of the listed bigrams.
+struct sctc_lexicon {
+    char* mem = nullptr;        // one allocation; the arrays below point into it
+    int32_t* child = nullptr;   // [nodes * A]: child node of (node, symbol), -1 for none
+    int32_t* word = nullptr;    // [nodes]: word id of the word ending here, -1 for none
+    float* ug = nullptr;        // [n_words] unigram value
+    float* bo = nullptr;        // [n_words] unigram back-off
+    uint64_t* bg_key = nullptr; // [bg_cap] (w1 << 32) | w2, all ones = empty
+    float* bg_val = nullptr;    // [bg_cap]
+    int64_t nodes = 0, n_words = 0, bg_cap = 0;
+    size_t bytes = 0;
+    int32_t A = 0, start = 0;
     int device = -1;
 };
 
@@ -63,7 +85,18 @@ struct BeamArgs {
     int32_t* ids;
     int32_t* lens;
     double* scores;
+    // the lexicon search only
+    const int32_t* lx_child;
+    const int32_t* lx_word;
+    const float* lx_ug;
+    const float* lx_bo;
+    const uint64_t* lx_key;
+    const float* lx_val;
+    uint64_t lx_mask;
+    int32_t lx_start, space;
 };
+
+constexpr uint64_t BG_EMPTY = ~0ull;
 
 // workspace slices are 256-byte aligned on both sides of the launch
 __host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -144,6 +177,39 @@ __device__ float lm_score(const BeamArgs& p, uint64_t ctx, int ctxlen, uint32_t 
     return best;
 }
 
+// bg_prob(w1, w2) of fastdecode/lm.cpp:119-127: the listed bigram, or -- when there is none or it
+// is exactly 0 -- the float32 sum back-off(w1) + unigram(w2)
+__device__ inline float lex_bg(const BeamArgs& p, int w1, int w2)
+{
+    const uint64_t key = ((uint64_t)(uint32_t)w1 << 32) | (uint32_t)w2;
+    uint64_t s = mix64(key) & p.lx_mask;
+    float v = 0.0f;
+    while (true) {
+        const uint64_t k = p.lx_key[s];
+        if (k == key) {
+            v = p.lx_val[s];
+            break;
+        }
+        if (k == BG_EMPTY) break;
+        s = (s + 1) & p.lx_mask;
+    }
+    if (v == 0.0f) v = p.lx_bo[w1] + p.lx_ug[w2];
+    return v;
+}
+
+// per beam entry of the lexicon search; a function of the prefix alone
+template <bool LEX>
+struct LexState {
+    int32_t node[KMAX];   // prefix-tree node the unfinished word has reached (0 = root)
+    int32_t pw[KMAX];     // id of the last finished word (<s> at the start)
+    int32_t nw[KMAX];     // finished words
+    int32_t wd[KMAX];     // word id of `node`, -1: a space cannot follow
+    float bg[KMAX];       // bg_prob(pw, wd): the LM value of the space extension, 0 without one
+};
+template <>
+struct LexState<false> {
+};
+
 struct Beam {
     uint64_t h[KMAX];     // prefix hash
     uint64_t ph[KMAX];    // hash of the prefix without its last symbol
@@ -205,9 +271,11 @@ __device__ inline double load_prob(const BeamArgs& p, int64_t row, int c)
     return p.f64 ? ((const double*)p.probs)[row * p.ld + c] : (double)((const float*)p.probs)[row * p.ld + c];
 }
 
-__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
+template <bool LEX>
+__device__ __forceinline__ void beam_search(const BeamArgs& p)
 {
     __shared__ Beam bm[2];
+    __shared__ LexState<LEX> lx[2];
     __shared__ HTab tab[2];
     __shared__ double y[AMAX];
     __shared__ int32_t par[KMAX];
@@ -221,7 +289,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
     const UttDesc u = p.utt[blockIdx.x];
     const int A = p.A, K = p.K, T = u.T;
     const int64_t M = (int64_t)K * A;
-    const bool has_lm = p.lm_key != nullptr;
+    const bool has_lm = !LEX && p.lm_key != nullptr;
     const int ctx_max = has_lm ? p.lm_order - 1 : 0;
     const uint64_t ctx_mask = bytes_mask(ctx_max);
 
@@ -248,6 +316,13 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
         bm[0].last[0] = -1;
         bm[0].len[0] = 0;
         bm[0].prev[0] = -1;
+        if constexpr (LEX) {
+            lx[0].node[0] = 0;
+            lx[0].pw[0] = p.lx_start;
+            lx[0].nw[0] = 0;
+            lx[0].wd[0] = p.lx_word[0];
+            lx[0].bg[0] = 0.0f;
+        }
     }
     __syncthreads();
     if (tid == 0) htab_insert(tab[0], H_EMPTY_PREFIX, 0);
@@ -260,6 +335,8 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
     for (int t = 0; t < T; ++t) {
         const Beam& B = bm[cb];
         Beam& NB = bm[cb ^ 1];
+        const LexState<LEX>& X = lx[cb];
+        LexState<LEX>& NX = lx[cb ^ 1];
         const HTab& cur = tab[tc];
         const HTab& old = tab[tc ^ 1];
         const int cw = t & 1, cr = cw ^ 1;
@@ -283,7 +360,9 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
                     const double t0 = v0 + y[l];
                     const int pj = par[j];
                     if (pj >= 0) {
-                        const double lmp = has_lm ? p.alpha * (double)rows[rb][pj * A + l] : 0.0;
+                        double lmp;
+                        if constexpr (LEX) lmp = l == p.space ? p.alpha * (double)X.bg[pj] : 0.0;
+                        else lmp = has_lm ? p.alpha * (double)rows[rb][pj * A + l] : 0.0;
                         const double e1 = (double)B.pb[pj] + y[l] + lmp;
                         const double e0 = B.last[pj] != l ? (double)B.pnb[pj] + y[l] + lmp : -INFINITY;
                         nb = lse3(t0, e0, e1);
@@ -293,14 +372,27 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
                 }
                 bb = lse2(v0 + y0, v1 + y0);
                 klen = B.len[j];
+                if constexpr (LEX) klen = X.nw[j];
             } else {
+                if constexpr (LEX) {
+                    // a space only after a whole word, a letter only along the tree: anything
+                    // else is no candidate (bg_decoder.pyx:48-61)
+                    const bool ok = c == p.space ? X.wd[j] >= 0 : p.lx_child[(int64_t)X.node[j] * A + c] >= 0;
+                    if (!ok) {
+                        ckey[idx] = 0;
+                        cand[cw][idx] = make_float2(-INFINITY, -INFINITY);
+                        continue;
+                    }
+                }
                 const uint64_t H = hstep(B.h[j], c);
                 if (htab_find(cur, H) >= 0) {          // P+c is a beam entry: counted there
                     ckey[idx] = 0;
                     cand[cw][idx] = make_float2(-INFINITY, -INFINITY);
                     continue;
                 }
-                const double lmw = has_lm ? p.alpha * (double)rows[rb][idx] : 0.0;
+                double lmw;
+                if constexpr (LEX) lmw = c == p.space ? p.alpha * (double)X.bg[j] : 0.0;
+                else lmw = has_lm ? p.alpha * (double)rows[rb][idx] : 0.0;
                 const double e1 = v1 + y[c] + lmw;
                 const double e0 = c != l ? v0 + y[c] + lmw : -INFINITY;
                 float2 hv = make_float2(-INFINITY, -INFINITY);
@@ -310,6 +402,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
                 nb = lse3(e0, e1, (double)hv.x + y[c]);
                 bb = lse2((double)hv.x + y0, (double)hv.y + y0);
                 klen = B.len[j] + 1;
+                if constexpr (LEX) klen = X.nw[j] + (c == p.space);
             }
             const double key = lse2(nb, bb) + p.beta * (double)klen;
             ckey[idx] = okey(key);
@@ -404,6 +497,13 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
                 NB.last[r] = B.last[j];
                 NB.len[r] = B.len[j];
                 NB.prev[r] = j;
+                if constexpr (LEX) {
+                    NX.node[r] = X.node[j];
+                    NX.pw[r] = X.pw[j];
+                    NX.nw[r] = X.nw[j];
+                    NX.wd[r] = X.wd[j];
+                    NX.bg[r] = X.bg[j];
+                }
             } else {
                 NB.h[r] = hstep(B.h[j], c);
                 NB.ph[r] = B.h[j];
@@ -411,6 +511,17 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
                 NB.last[r] = c;
                 NB.len[r] = B.len[j] + 1;
                 NB.prev[r] = -1;
+                if constexpr (LEX) {
+                    const bool sp = c == p.space;
+                    const int nd = sp ? 0 : p.lx_child[(int64_t)X.node[j] * A + c];
+                    const int pw = sp ? X.wd[j] : X.pw[j];
+                    const int wd = p.lx_word[nd];
+                    NX.node[r] = nd;
+                    NX.pw[r] = pw;
+                    NX.nw[r] = X.nw[j] + sp;
+                    NX.wd[r] = wd;
+                    NX.bg[r] = wd >= 0 ? lex_bg(p, pw, wd) : 0.0f;
+                }
             }
             rec[(int64_t)t * K + r] = (j << 16) | c;
         }
@@ -461,6 +572,10 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p)
     }
 }
 
+__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p) { beam_search<false>(p); }
+
+__global__ __launch_bounds__(NT) void ctc_lexbeam_kernel(BeamArgs p) { beam_search<true>(p); }
+
 struct BeamPlan {
     std::vector<UttDesc> utt;
     size_t head = 0;     // descriptors + symbol map
@@ -506,6 +621,28 @@ int plan_beam(const sctc_beam_config* cfg, BeamPlan& pl)
     }
     pl.total = off;
     return SCTC_OK;
+}
+
+// the lexicon search plans like the character search without an LM: the same workspace
+int plan_lexbeam(const sctc_lexbeam_config* cfg, BeamPlan& pl)
+{
+    SCTC_CHECK_ARG(cfg, "lexbeam: null config");
+    SCTC_CHECK_ARG(cfg->lexicon, "lexbeam: null lexicon");
+    SCTC_CHECK_ARG(cfg->A == cfg->lexicon->A, "lexbeam: alphabet size %d, the lexicon was built for %d", cfg->A,
+                   cfg->lexicon->A);
+    SCTC_CHECK_ARG(cfg->space >= 1 && cfg->space < cfg->A, "lexbeam: space symbol %d outside 1..A-1", cfg->space);
+    sctc_beam_config c{};
+    c.B = cfg->B;
+    c.A = cfg->A;
+    c.dtype = cfg->dtype;
+    c.beam = cfg->beam;
+    c.nbest = cfg->nbest;
+    c.ld = cfg->ld;
+    c.T_b = cfg->T_b;
+    c.frame_off = cfg->frame_off;
+    c.alpha = cfg->alpha;
+    c.beta = cfg->beta;
+    return plan_beam(&c, pl);
 }
 
 }  // namespace
@@ -612,6 +749,154 @@ int sctc_ctc_beam_decode_batch(const sctc_beam_config* cfg, const void* probs_de
     a.lens = lengths_dev;
     a.scores = scores_dev;
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(cfg->B), dim3(NT), 0, s, a);
+    SCTC_HIP_TRY(hipGetLastError());
+    return SCTC_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int sctc_lexicon_create(const int32_t* child_host, const int32_t* word_host, int64_t nodes, int32_t A,
+                        int32_t space, const float* ug_prob_host, const float* ug_backoff_host, int64_t n_words,
+                        const uint64_t* bg_keys_host, const float* bg_vals_host, int64_t bg_capacity,
+                        int32_t start_word, sctc_lexicon_t* out)
+{
+    SCTC_CHECK_ARG(out, "lexicon: null argument");
+    *out = nullptr;
+    SCTC_CHECK_ARG(child_host && word_host && ug_prob_host && ug_backoff_host && bg_keys_host && bg_vals_host,
+                   "lexicon: null argument");
+    SCTC_CHECK_ARG(A >= 2 && A <= AMAX, "lexicon: alphabet size %d outside 2..%d", A, AMAX);
+    SCTC_CHECK_ARG(space >= 1 && space < A, "lexicon: space symbol %d outside 1..A-1", space);
+    SCTC_CHECK_ARG(nodes >= 1 && nodes <= (int64_t)INT32_MAX / A, "lexicon: %lld nodes outside 1..2^31/A",
+                   (long long)nodes);
+    SCTC_CHECK_ARG(n_words >= 1 && n_words <= INT32_MAX, "lexicon: %lld words", (long long)n_words);
+    SCTC_CHECK_ARG(start_word >= 0 && start_word < n_words, "lexicon: <s> word id %d outside the vocabulary",
+                   start_word);
+    SCTC_CHECK_ARG(bg_capacity >= 2 && (bg_capacity & (bg_capacity - 1)) == 0,
+                   "lexicon: bigram capacity %lld not a power of two", (long long)bg_capacity);
+    // everything the kernel follows without a check of its own is checked here, once
+    SCTC_CHECK_ARG(word_host[0] < 0, "lexicon: the root is a word");
+    for (int64_t n = 0; n < nodes; ++n) {
+        SCTC_CHECK_ARG(word_host[n] >= -1 && word_host[n] < n_words, "lexicon: node %lld has word id %d", (long long)n,
+                       word_host[n]);
+        SCTC_CHECK_ARG(child_host[n * A] < 0 && child_host[n * A + space] < 0,
+                       "lexicon: node %lld has a child for the blank or the space", (long long)n);
+        for (int c = 1; c < A; ++c) {
+            const int32_t ch = child_host[n * A + c];
+            SCTC_CHECK_ARG(ch >= -1 && ch < nodes && ch != 0, "lexicon: node %lld symbol %d -> node %d", (long long)n, c, ch);
+        }
+    }
+    int64_t used = 0;
+    for (int64_t i = 0; i < bg_capacity; ++i) {
+        const uint64_t k = bg_keys_host[i];
+        if (k == BG_EMPTY) continue;
+        ++used;
+        SCTC_CHECK_ARG((int64_t)(k >> 32) < n_words && (int64_t)(k & 0xFFFFFFFFull) < n_words,
+                       "lexicon: bigram slot %lld names a word outside the vocabulary", (long long)i);
+    }
+    SCTC_CHECK_ARG(used < bg_capacity, "lexicon: bigram table without an empty slot");
+    int dev = 0;
+    SCTC_HIP_TRY(hipGetDevice(&dev));
+    const size_t sz[6] = {al256((size_t)nodes * A * sizeof(int32_t)), al256((size_t)nodes * sizeof(int32_t)),
+                          al256((size_t)n_words * sizeof(float)),     al256((size_t)n_words * sizeof(float)),
+                          al256((size_t)bg_capacity * sizeof(uint64_t)), al256((size_t)bg_capacity * sizeof(float))};
+    const size_t raw[6] = {(size_t)nodes * A * sizeof(int32_t), (size_t)nodes * sizeof(int32_t),
+                           (size_t)n_words * sizeof(float),     (size_t)n_words * sizeof(float),
+                           (size_t)bg_capacity * sizeof(uint64_t), (size_t)bg_capacity * sizeof(float)};
+    const void* src[6] = {child_host, word_host, ug_prob_host, ug_backoff_host, bg_keys_host, bg_vals_host};
+    size_t total = 0, off[6];
+    for (int i = 0; i < 6; ++i) {
+        off[i] = total;
+        total += sz[i];
+    }
+    void* mem = nullptr;
+    hipError_t e = hipMalloc(&mem, total);
+    for (int i = 0; i < 6 && e == hipSuccess; ++i)
+        e = hipMemcpy((char*)mem + off[i], src[i], raw[i], hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (mem) (void)hipFree(mem);
+        return set_error(SCTC_ERR_HIP, "lexicon: upload failed: %s", hipGetErrorString(e));
+    }
+    sctc_lexicon* lx = new sctc_lexicon();
+    lx->mem = (char*)mem;
+    lx->child = (int32_t*)(lx->mem + off[0]);
+    lx->word = (int32_t*)(lx->mem + off[1]);
+    lx->ug = (float*)(lx->mem + off[2]);
+    lx->bo = (float*)(lx->mem + off[3]);
+    lx->bg_key = (uint64_t*)(lx->mem + off[4]);
+    lx->bg_val = (float*)(lx->mem + off[5]);
+    lx->nodes = nodes;
+    lx->n_words = n_words;
+    lx->bg_cap = bg_capacity;
+    lx->bytes = total;
+    lx->A = A;
+    lx->start = start_word;
+    lx->device = dev;
+    *out = lx;
+    return SCTC_OK;
+}
+
+int sctc_lexicon_destroy(sctc_lexicon_t lexicon)
+{
+    if (!lexicon) return SCTC_OK;
+    if (lexicon->mem) (void)hipFree(lexicon->mem);
+    delete lexicon;
+    return SCTC_OK;
+}
+
+size_t sctc_lexicon_bytes(sctc_lexicon_t lexicon) { return lexicon ? lexicon->bytes : 0; }
+
+size_t sctc_ctc_lexbeam_workspace_bytes(const sctc_lexbeam_config* cfg)
+{
+    BeamPlan pl;
+    if (plan_lexbeam(cfg, pl) != SCTC_OK) return 0;
+    return pl.total;
+}
+
+int sctc_ctc_lexbeam_decode_batch(const sctc_lexbeam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                                  int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                                  size_t workspace_bytes, void* stream)
+{
+    BeamPlan pl;
+    SCTC_TRY(plan_lexbeam(cfg, pl));
+    SCTC_CHECK_ARG(probs_dev && lengths_dev && scores_dev && workspace_dev, "lexbeam: null device pointer");
+    int64_t total_T = 0;
+    for (int b = 0; b < cfg->B; ++b) total_T += cfg->T_b[b];
+    SCTC_CHECK_ARG(ids_dev || total_T == 0, "lexbeam: null ids");
+    if (workspace_bytes < pl.total)
+        return set_error(SCTC_ERR_WORKSPACE, "lexbeam: workspace %zu bytes < %zu needed", workspace_bytes, pl.total);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<char> head(pl.head, 0);
+    memcpy(head.data(), pl.utt.data(), cfg->B * sizeof(UttDesc));
+    SCTC_HIP_TRY(hipMemcpyAsync(workspace_dev, head.data(), pl.head, hipMemcpyHostToDevice, s));
+    SCTC_HIP_TRY(hipStreamSynchronize(s));
+
+    const sctc_lexicon* lx = cfg->lexicon;
+    BeamArgs a{};
+    a.probs = probs_dev;
+    a.ld = cfg->ld;
+    a.f64 = cfg->dtype == SCTC_F64;
+    a.A = cfg->A;
+    a.K = cfg->beam;
+    a.nbest = cfg->nbest;
+    a.alpha = cfg->alpha;
+    a.beta = cfg->beta;
+    a.utt = (const UttDesc*)workspace_dev;
+    a.ws = (char*)workspace_dev;
+    a.ids = ids_dev;
+    a.lens = lengths_dev;
+    a.scores = scores_dev;
+    a.lx_child = lx->child;
+    a.lx_word = lx->word;
+    a.lx_ug = lx->ug;
+    a.lx_bo = lx->bo;
+    a.lx_key = lx->bg_key;
+    a.lx_val = lx->bg_val;
+    a.lx_mask = (uint64_t)(lx->bg_cap - 1);
+    a.lx_start = lx->start;
+    a.space = cfg->space;
+    hipLaunchKernelGGL(ctc_lexbeam_kernel, dim3(cfg->B), dim3(NT), 0, s, a);
     SCTC_HIP_TRY(hipGetLastError());
     return SCTC_OK;
 }

@@ -212,57 +212,40 @@ class DecodeLM(object):
             pass
 
 
-def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=None, nbest=1):
-    """CTC prefix beam search with an optional character LM, batched (DESIGN.md §4.5): the
-    reference's ``BeamLMDecoder.decode`` (ctc_fast/new_decoder/decoder.pyx:136-193) for every
-    utterance at once, one workgroup per utterance.
-
-    logprobs: list of (A, T_b) float32/float64 natural-log probability arrays (symbol 0 the
-    blank), or a torch device tensor [sum T][A] with ``lengths`` giving T_b.  lm: a
-    :class:`DecodeLM` or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
-    of int32 symbol-id arrays and float64[B]; with nbest > 1 a list of lists and [B, nbest]
-    (entries beyond the beam: empty, -inf)."""
+def _decode_inputs(logprobs, lengths, what):
+    """(host arrays or None, device tensor or None, A, T_b, numpy dtype, sctc dtype) of a decode call"""
     import torch
     if isinstance(logprobs, torch.Tensor):
         if lengths is None:
-            raise ValueError("decode_beam_batch: a device tensor needs lengths")
+            raise ValueError("%s: a device tensor needs lengths" % what)
         if logprobs.dim() != 2:
-            raise ValueError("decode_beam_batch: expected a [sum T][A] tensor")
+            raise ValueError("%s: expected a [sum T][A] tensor" % what)
         T_b = [int(t) for t in lengths]
         A = int(logprobs.shape[1])
-        src = logprobs
-        if src.dtype not in (torch.float32, torch.float64):
+        if logprobs.dtype not in (torch.float32, torch.float64):
             raise ValueError("Buffer dtype mismatch, expected 'double' or 'float'")
-        dtype = _sctc.F64 if src.dtype == torch.float64 else _sctc.F32
-        if sum(T_b) > src.shape[0]:
-            raise ValueError("decode_beam_batch: lengths exceed the tensor's rows")
-    else:
-        arrs = [np.asarray(p) for p in logprobs]
-        if not arrs:
-            raise ValueError("decode_beam_batch: empty batch")
-        for p in arrs:
-            if p.ndim != 2 or p.shape[0] != arrs[0].shape[0]:
-                raise ValueError("decode_beam_batch: every utterance must be an (A, T) array of one A")
-        A = arrs[0].shape[0]
-        T_b = [p.shape[1] for p in arrs]
-        dt = np.float64 if any(p.dtype == np.float64 for p in arrs) else np.float32
-        dtype = _sctc.F64 if dt == np.float64 else _sctc.F32
-        src = None
+        dtype = _sctc.F64 if logprobs.dtype == torch.float64 else _sctc.F32
+        if sum(T_b) > logprobs.shape[0]:
+            raise ValueError("%s: lengths exceed the tensor's rows" % what)
+        return None, logprobs, A, T_b, None, dtype
+    arrs = [np.asarray(p) for p in logprobs]
+    if not arrs:
+        raise ValueError("%s: empty batch" % what)
+    for p in arrs:
+        if p.ndim != 2 or p.shape[0] != arrs[0].shape[0]:
+            raise ValueError("%s: every utterance must be an (A, T) array of one A" % what)
+    A = arrs[0].shape[0]
+    T_b = [p.shape[1] for p in arrs]
+    dt = np.float64 if any(p.dtype == np.float64 for p in arrs) else np.float32
+    return arrs, None, A, T_b, dt, _sctc.F64 if dt == np.float64 else _sctc.F32
+
+
+def _decode_launch(cfg, bytes_fn, decode_fn, arrs, src, A, T_b, dt, nbest, what):
+    """workspace, upload, launch and read-back shared by the two beam searches"""
     B = len(T_b)
-    if lm is not None and not isinstance(lm, DecodeLM):
-        raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM or None")
-    if lm is not None and lm.sym_words.shape[0] < A:
-        raise ValueError("decode_beam_batch: the LM maps %d symbols, the input has %d"
-                         % (lm.sym_words.shape[0], A))
-    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
-    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(T_b)[:-1]]) if B else [], dtype=np.int64)
-    sw = np.ascontiguousarray(lm.sym_words[:A] if lm is not None else np.zeros(A, np.int32), dtype=np.int32)
-    cfg = _sctc.BeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
-                           float(alpha), float(beta), lm.handle if lm is not None else None, _sctc.i32(sw))
-    L = _sctc.lib()
-    nbytes = L.sctc_ctc_beam_workspace_bytes(ctypes.byref(cfg))
+    nbytes = bytes_fn(ctypes.byref(cfg))
     if nbytes == 0:
-        _sctc.check(-1, "decode_beam_batch")
+        _sctc.check(-1, what)
     torch = _sctc.require_gpu()
     if src is None:
         host = np.concatenate([np.ascontiguousarray(p.T, dtype=dt) for p in arrs], axis=0) if sum(T_b) else \
@@ -275,9 +258,9 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
     ids = torch.zeros(max(1, nbest * sum(T_b)), dtype=torch.int32, device=dev.device)
     lens = torch.empty(B * nbest, dtype=torch.int32, device=dev.device)
     scores = torch.empty(B * nbest, dtype=torch.float64, device=dev.device)
-    rc = L.sctc_ctc_beam_decode_batch(ctypes.byref(cfg), dev.data_ptr(), ids.data_ptr(), lens.data_ptr(),
-                                      scores.data_ptr(), ws.data_ptr(), nbytes, _sctc.current_stream_ptr())
-    _sctc.check(rc, "decode_beam_batch")
+    rc = decode_fn(ctypes.byref(cfg), dev.data_ptr(), ids.data_ptr(), lens.data_ptr(),
+                   scores.data_ptr(), ws.data_ptr(), nbytes, _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
     ids, lens, scores = ids.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy()
     hyps = []
     base = 0
@@ -291,3 +274,110 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
     if nbest == 1:
         return [h[0] for h in hyps], scores
     return hyps, scores.reshape(B, nbest)
+
+
+def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=None, nbest=1):
+    """CTC prefix beam search with an optional character LM, batched (DESIGN.md §4.5): the
+    reference's ``BeamLMDecoder.decode`` (ctc_fast/new_decoder/decoder.pyx:136-193) for every
+    utterance at once, one workgroup per utterance.
+
+    logprobs: list of (A, T_b) float32/float64 natural-log probability arrays (symbol 0 the
+    blank), or a torch device tensor [sum T][A] with ``lengths`` giving T_b.  lm: a
+    :class:`DecodeLM` or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
+    of int32 symbol-id arrays and float64[B]; with nbest > 1 a list of lists and [B, nbest]
+    (entries beyond the beam: empty, -inf)."""
+    arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, "decode_beam_batch")
+    B = len(T_b)
+    if lm is not None and not isinstance(lm, DecodeLM):
+        raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM or None")
+    if lm is not None and lm.sym_words.shape[0] < A:
+        raise ValueError("decode_beam_batch: the LM maps %d symbols, the input has %d"
+                         % (lm.sym_words.shape[0], A))
+    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(T_b)[:-1]]) if B else [], dtype=np.int64)
+    sw = np.ascontiguousarray(lm.sym_words[:A] if lm is not None else np.zeros(A, np.int32), dtype=np.int32)
+    cfg = _sctc.BeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
+                           float(alpha), float(beta), lm.handle if lm is not None else None, _sctc.i32(sw))
+    L = _sctc.lib()
+    return _decode_launch(cfg, L.sctc_ctc_beam_workspace_bytes, L.sctc_ctc_beam_decode_batch, arrs, src, A, T_b,
+                          dt, nbest, "decode_beam_batch")
+
+
+class DecodeLexicon(object):
+    """A lexicon on the device for :func:`decode_lexicon_beam_batch`: the prefix tree of
+    ``words`` (plus ``specials``, tokens that are whole words) and the word-bigram LM ``arpa``
+    (a :class:`decoder.lm.LM` or the path of an ARPA file), flattened and uploaded once.
+
+    chars: {token: symbol id} or the path of a ``token id`` file; words: a list or the path of a
+    word list; space: the separator token or its symbol id; A: the alphabet size of the inputs
+    (default: the largest symbol id + 1)."""
+
+    def __init__(self, words, chars, arpa, space, specials=(), A=None):
+        from decoder import decoder_utils, lm as lm_mod, prefixTree
+        if isinstance(chars, str):
+            chars = decoder_utils.load_chars(chars)
+        if isinstance(words, str):
+            words = decoder_utils.load_words(words)
+        if not isinstance(arpa, lm_mod.LM):
+            arpa = lm_mod.LM(arpa)
+        tree = prefixTree.PrefixTree(chars, words, arpa, specials=specials, space=space)
+        self.handle = None
+        self._upload(tree, arpa, int(A) if A is not None else max(chars.values()) + 1)
+
+    @classmethod
+    def from_tree(cls, tree, lm, A):
+        """from a built :class:`decoder.prefixTree.PrefixTree` and its LM"""
+        self = cls.__new__(cls)
+        self.handle = None
+        self._upload(tree, lm, int(A))
+        return self
+
+    def _upload(self, tree, lm, A):
+        self.tree, self.lm, self.A, self.space = tree, lm, A, int(tree.space)
+        child, word = tree.flatten(A)
+        keys, vals = lm.pack_bigrams()
+        self.nodes = child.shape[0]
+        _sctc.require_gpu()
+        h = ctypes.c_void_p()
+        ug = np.ascontiguousarray(lm.ug, dtype=np.float32)
+        bo = np.ascontiguousarray(lm.bo, dtype=np.float32)
+        rc = _sctc.lib().sctc_lexicon_create(child.ctypes.data, word.ctypes.data, child.shape[0], A, self.space,
+                                             ug.ctypes.data, bo.ctypes.data, ug.shape[0], keys.ctypes.data,
+                                             vals.ctypes.data, keys.shape[0], int(lm.start), ctypes.byref(h))
+        _sctc.check(rc, "DecodeLexicon")
+        self.handle = h
+        self.device_bytes = int(_sctc.lib().sctc_lexicon_bytes(h))
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            _sctc.lib().sctc_lexicon_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_lexicon_beam_batch(logprobs, lengths=None, lexicon=None, beam=40, alpha=1.0, beta=0.0, nbest=1):
+    """Lexicon-constrained CTC prefix beam search with a word-bigram LM, batched (DESIGN.md
+    §4.6): the reference's ``decode_bg_lm`` (ctc_fast/decoder/bg_decoder.pyx:18-95) for every
+    utterance at once, one workgroup per utterance.  Inputs and outputs as
+    :func:`decode_beam_batch`; lexicon: a :class:`DecodeLexicon`.  A hypothesis spells lexicon
+    words separated by the space symbol and may end inside a word; its score is
+    log(p_nb + p_b) + beta * (words finished)."""
+    if not isinstance(lexicon, DecodeLexicon):
+        raise ValueError("decode_lexicon_beam_batch: lexicon must be a ctc_fast.DecodeLexicon")
+    arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, "decode_lexicon_beam_batch")
+    if A != lexicon.A:
+        raise ValueError("decode_lexicon_beam_batch: the lexicon was built for %d symbols, the input has %d"
+                         % (lexicon.A, A))
+    B = len(T_b)
+    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(T_b)[:-1]]) if B else [], dtype=np.int64)
+    cfg = _sctc.LexBeamConfig(B, int(A), dtype, int(beam), int(nbest), lexicon.space, int(A), _sctc.i32(Tb),
+                              _sctc.i64(off), float(alpha), float(beta), lexicon.handle)
+    L = _sctc.lib()
+    return _decode_launch(cfg, L.sctc_ctc_lexbeam_workspace_bytes, L.sctc_ctc_lexbeam_decode_batch, arrs, src, A,
+                          T_b, dt, nbest, "decode_lexicon_beam_batch")

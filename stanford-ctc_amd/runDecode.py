@@ -6,6 +6,14 @@ rate against the alignments (Wagner-Fischer on the host).
 
     python runDecode.py --likelihoods loglikelihoods_1.pk --chars chars.txt --alis alis1.txt \\
         --lm text_char.2g.arpa --out hyps.txt [--beam 40 --alpha 1.0 --beta 0.0 --batch 256]
+
+``--method bg`` decodes to words instead (the reference's ``decoder_utils.decode(..., method='bg')``,
+ctc_fast/decoder/bg_decoder.pyx): a word list constrains the spellings, an ARPA word-bigram LM
+scores every finished word, hypotheses are written as words, and the word error rate is reported
+next to the character error rate (reference words: the alignment split at the space symbol).
+
+    python runDecode.py --method bg --likelihoods loglikelihoods_1.pk --chars chars.txt --alis alis1.txt \\
+        --words wordlist --word-lm text_word.2g.arpa --out hyps.txt [--specials [noise] [laughter]]
 """
 import argparse
 import os
@@ -17,6 +25,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from new_decoder import decoder  # noqa: E402
+from decoder import decoder_utils  # noqa: E402
 
 
 def edit_distance(ref, hyp):
@@ -60,12 +69,47 @@ def tokens(hyp, char_int_map):
     return toks
 
 
+def decode_bg(a, ll):
+    """--method bg: (CER, WER) of the lexicon-constrained word-bigram search"""
+    import ctc_fast
+    chars = decoder_utils.load_chars(a.chars)
+    alis = load_alis(a.alis, a.chars)
+    lex = ctc_fast.DecodeLexicon(a.words, chars, a.word_lm, a.space, specials=a.specials)
+    keys = sorted(ll)
+    errs = n_ref = werrs = n_words = 0
+    with open(a.out, "w") as out:
+        for g in range(0, len(keys), a.batch):
+            ks = keys[g:g + a.batch]
+            hyps, scores = ctc_fast.decode_lexicon_beam_batch([np.asarray(ll[k]) for k in ks], lexicon=lex,
+                                                              beam=a.beam, alpha=a.alpha, beta=a.beta)
+            for k, ids, score in zip(ks, hyps, scores):
+                toks = decoder_utils.int_to_char(ids, chars)
+                out.write("%s %.6f %s\n" % (k, score, decoder_utils.collapse_seq(toks, a.space)))
+                if k in alis:
+                    errs += edit_distance(alis[k], toks)
+                    n_ref += len(alis[k])
+                    ref_words = decoder_utils.collapse_seq(alis[k], a.space).split()
+                    werrs += edit_distance(ref_words, decoder_utils.collapse_seq(toks, a.space).split())
+                    n_words += len(ref_words)
+    cer = errs / float(max(n_ref, 1))
+    wer = werrs / float(max(n_words, 1))
+    print("decoded %d utterances, CER %.4f (%d / %d), WER %.4f (%d / %d)"
+          % (len(keys), cer, errs, n_ref, wer, werrs, n_words))
+    return cer, wer
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--likelihoods", required=True)
     ap.add_argument("--chars", required=True)
     ap.add_argument("--alis", required=True)
-    ap.add_argument("--lm", required=True)
+    ap.add_argument("--lm", help="ARPA character LM (the default method)")
+    ap.add_argument("--method", choices=("char", "bg"), default="char",
+                    help="char: character LM (default); bg: word list and word-bigram LM")
+    ap.add_argument("--words", help="word list, one per line (--method bg)")
+    ap.add_argument("--word-lm", help="ARPA word-bigram LM (--method bg)")
+    ap.add_argument("--specials", nargs="*", default=[], help="tokens of chars.txt that are whole words")
+    ap.add_argument("--space", default="[space]", help="the word separator token of chars.txt")
     ap.add_argument("--out", required=True)
     ap.add_argument("--beam", type=int, default=40)
     ap.add_argument("--alpha", type=float, default=1.0)
@@ -74,6 +118,12 @@ def main(argv=None):
     a = ap.parse_args(argv)
     with open(a.likelihoods, "rb") as f:
         ll = pickle.load(f)
+    if a.method == "bg":
+        if not a.words or not a.word_lm:
+            ap.error("--method bg needs --words and --word-lm")
+        return decode_bg(a, ll)
+    if not a.lm:
+        ap.error("--lm is required")
     alis = load_alis(a.alis, a.chars)
     dec = decoder.BeamLMDecoder()
     dec.load_chars(a.chars)
