@@ -229,6 +229,64 @@ int sctc_ctc_lexbeam_decode_batch(const sctc_lexbeam_config* cfg, const void* pr
                                   int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- decoding with a neural character LM: ctc_fast/decoder/clm_decoder2.pyx -----
+ * Added without an ABI version bump (still 6): sctc_nnlm_create / sctc_nnlm_destroy / sctc_nnlm_bytes /
+ * sctc_nnlm_rows, sctc_ctc_nnbeam_workspace_bytes, sctc_ctc_nnbeam_decode_batch. */
+
+/* A fixed-window feed-forward character LM on the device (stanford-ctc_amd/nn_lm.py holds the model
+ * file).  The input is `context` one-hot vectors over `vocab` ids, oldest slot first, so column
+ * slot * vocab + id of the first matrix; every hidden layer is relu(W h + b), the output layer is
+ * linear and a row is log10 softmax of it.  All float32, the log-softmax in float64.
+ *   vocab 3..256, context 1..32, n_layers 2..5 weight matrices (1..4 hidden layers and the output)
+ *   widths[n_layers + 1]   widths[0] = context * vocab, widths[n_layers] = vocab, the hidden widths
+ *                          between them multiples of 32 up to 2048 (pad with zero units: relu(0) = 0)
+ *   weights_host[l]        row-major [widths[l + 1]][widths[l]];  biases_host[l] [widths[l + 1]]
+ *   bos_id / null_id       the ids of <s> and <null>: a prefix shorter than the context is preceded
+ *                          by <s>, every older slot holds <null> (clm_decoder2.pyx:52-54)
+ * The one allocating call: the parameters are repacked and uploaded, and the scratch of
+ * sctc_nnlm_rows is part of the handle, which lives until sctc_nnlm_destroy. */
+typedef struct sctc_nnlm* sctc_nnlm_t;
+int sctc_nnlm_create(int32_t vocab, int32_t context, int32_t n_layers, const int32_t* widths,
+                     const float* const* weights_host, const float* const* biases_host, int32_t bos_id,
+                     int32_t null_id, sctc_nnlm_t* out);
+int sctc_nnlm_destroy(sctc_nnlm_t lm);
+/* bytes of device memory the LM holds (0 for NULL) */
+size_t sctc_nnlm_bytes(sctc_nnlm_t lm);
+
+/* rows_dev[i * vocab + v] = log10 P(v | contexts_dev[i * context .. + context - 1]) for n contexts of LM
+ * ids, oldest first (an id outside 0..vocab-1 is clamped into it).  A row is a function of its context
+ * alone, to the bit: not of n, of its position, or of who asks (the search evaluates the same routine).
+ * Allocates nothing; calls on one handle share its scratch and must be ordered on one stream. */
+int sctc_nnlm_rows(sctc_nnlm_t lm, const int32_t* contexts_dev, int64_t n, float* rows_dev, void* stream);
+
+/* The prefix beam search of sctc_ctc_beam_decode_batch with the LM term alpha * log10 P_NN(c | window of
+ * <null>.. <s> prefix).  The fields of sctc_beam_config, the LM handle apart. */
+typedef struct sctc_nnbeam_config {
+    int32_t B;                 /* utterances */
+    int32_t A;                 /* symbols incl. blank, 2..256 */
+    int32_t dtype;             /* SCTC_F32 | SCTC_F64: type of probs */
+    int32_t beam;              /* 1..256 */
+    int32_t nbest;             /* hypotheses returned per utterance, 1..beam */
+    int32_t reserved;          /* 0 */
+    int64_t ld;                /* row stride of probs in elements (>= A) */
+    const int32_t* T_b;        /* host [B] */
+    const int64_t* frame_off;  /* host [B] */
+    double alpha;              /* LM weight */
+    double beta;               /* length bonus */
+    sctc_nnlm_t lm;            /* required */
+    const int32_t* sym_word;   /* host [A]: LM id (0..vocab-1) of symbols 1..A-1 */
+} sctc_nnbeam_config;
+
+/* bytes of device workspace (0: rejected, sctc_last_error()): per utterance what
+ * sctc_ctc_beam_workspace_bytes reports with an LM, 64 * beam bytes of context windows and one tile of
+ * the LM (256 * widest hidden layer + 128 * (vocab padded to 32) + 128 * context bytes) */
+size_t sctc_ctc_nnbeam_workspace_bytes(const sctc_nnbeam_config* cfg);
+
+/* Outputs as sctc_ctc_beam_decode_batch writes them.  Allocates nothing. */
+int sctc_ctc_nnbeam_decode_batch(const sctc_nnbeam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                                 int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

@@ -63,6 +63,14 @@ class LexBeamConfig(ctypes.Structure):
                 ("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("lexicon", vp)]
 
 
+class NNBeamConfig(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("A", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("beam", ctypes.c_int32), ("nbest", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("ld", ctypes.c_int64), ("T_b", c_i32p), ("frame_off", c_i64p),
+                ("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("lm", vp),
+                ("sym_word", c_i32p)]
+
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -95,6 +103,14 @@ PROTOTYPES = {
     "sctc_ctc_lexbeam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(LexBeamConfig)]),
     "sctc_ctc_lexbeam_decode_batch": (ctypes.c_int, [ctypes.POINTER(LexBeamConfig), vp, vp, vp, vp, vp,
                                                      ctypes.c_size_t, vp]),
+    "sctc_nnlm_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i32p, ctypes.POINTER(vp),
+                                        ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]),
+    "sctc_nnlm_destroy": (ctypes.c_int, [vp]),
+    "sctc_nnlm_bytes": (ctypes.c_size_t, [vp]),
+    "sctc_nnlm_rows": (ctypes.c_int, [vp, vp, ctypes.c_int64, vp, vp]),
+    "sctc_ctc_nnbeam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(NNBeamConfig)]),
+    "sctc_ctc_nnbeam_decode_batch": (ctypes.c_int, [ctypes.POINTER(NNBeamConfig), vp, vp, vp, vp, vp,
+                                                    ctypes.c_size_t, vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),

@@ -19,11 +19,18 @@
 // carries its prefix-tree node, the previous word, the word count and the cached bigram term of
 // its space extension; an extension the tree forbids is no candidate, the LM term is the word
 // bigram at a space, and the length bonus counts words.
+//
+// A third instantiation (NN) is the character search with a neural LM as the provider of the rows
+// (the lexicon-free path of the reference's ctc_fast/decoder/clm_decoder2.pyx): every
+// beam entry carries the window of the last K LM ids of <null>.. <s> + P, copied from its parent and
+// shifted on extension, and step 4 evaluates the rows of the new entries in tiles of 32 through
+// nnlm_tile (nnlm_dev.h), the routine sctc_nnlm_rows runs.
 #include <math.h>
 
 #include <vector>
 
 #include "common.h"
+#include "nnlm_dev.h"
 
 struct sctc_lm {
     uint64_t* key = nullptr;   // device [cap]; prob / backoff follow in the same allocation
@@ -97,6 +104,14 @@ struct BeamArgs {
 };
 
 constexpr uint64_t BG_EMPTY = ~0ull;
+
+// the neural LM search only: a kernel argument of its own, BeamArgs stays as the other two read it
+struct NNArgs {
+    NNLMDev m;
+};
+struct NoNNArgs {
+};
+constexpr int WIN = NN_MAX_CONTEXT;   // bytes of a beam entry's context window (one LM id per byte)
 
 // workspace slices are 256-byte aligned on both sides of the launch
 __host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -271,8 +286,8 @@ __device__ inline double load_prob(const BeamArgs& p, int64_t row, int c)
     return p.f64 ? ((const double*)p.probs)[row * p.ld + c] : (double)((const float*)p.probs)[row * p.ld + c];
 }
 
-template <bool LEX>
-__device__ __forceinline__ void beam_search(const BeamArgs& p)
+template <bool LEX, bool NN, typename NNA>
+__device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
 {
     __shared__ Beam bm[2];
     __shared__ LexState<LEX> lx[2];
@@ -289,7 +304,7 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p)
     const UttDesc u = p.utt[blockIdx.x];
     const int A = p.A, K = p.K, T = u.T;
     const int64_t M = (int64_t)K * A;
-    const bool has_lm = !LEX && p.lm_key != nullptr;
+    const bool has_lm = NN || (!LEX && p.lm_key != nullptr);
     const int ctx_max = has_lm ? p.lm_order - 1 : 0;
     const uint64_t ctx_mask = bytes_mask(ctx_max);
 
@@ -300,6 +315,20 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p)
     w += al256(M * sizeof(uint64_t));
     float* rows[2] = {(float*)w, (float*)w + M};
     if (has_lm) w += al256(2 * M * sizeof(float));
+    // NN: the context windows of both beams, then the scratch of one LM tile
+    uint8_t* win[2] = {nullptr, nullptr};
+    float* nn_act = nullptr;
+    float* nn_rows = nullptr;
+    int32_t* nn_ids = nullptr;
+    if constexpr (NN) {
+        win[0] = (uint8_t*)w;
+        win[1] = win[0] + (size_t)K * WIN;
+        w += al256((size_t)2 * K * WIN);
+        nn_act = (float*)w;
+        nn_rows = (float*)(w + nn_act_bytes(nn.m.hmax));
+        nn_ids = (int32_t*)(w + nn_act_bytes(nn.m.hmax) + nn_row_bytes(nn.m.Vp));
+        w += nn_tile_bytes(nn.m.hmax, nn.m.Vp, nn.m.K);
+    }
     int32_t* rec = (int32_t*)w;
 
     for (int s = tid; s < HT; s += NT) {
@@ -326,9 +355,22 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p)
     }
     __syncthreads();
     if (tid == 0) htab_insert(tab[0], H_EMPTY_PREFIX, 0);
-    if (has_lm)
-        for (int c = tid; c < A; c += NT)
-            rows[0][c] = c == 0 ? 0.0f : lm_score(p, bm[0].ctx[0], ctx_max < 1 ? ctx_max : 1, (uint32_t)p.sym_word[c]);
+    if constexpr (NN) {
+        // the empty prefix: <null> .. <null> <s>
+        const int CK = nn.m.K;
+        for (int s = tid; s < CK; s += NT) {
+            const int id = s == CK - 1 ? nn.m.bos : nn.m.null_id;
+            win[0][s] = (uint8_t)id;
+            nn_ids[s] = id;
+        }
+        __syncthreads();
+        nnlm_tile(nn.m, nn_ids, 1, nn_act, nn_rows);
+        for (int c = tid; c < A; c += NT) rows[0][c] = c == 0 ? 0.0f : nn_rows[p.sym_word[c]];
+    } else {
+        if (has_lm)
+            for (int c = tid; c < A; c += NT)
+                rows[0][c] = c == 0 ? 0.0f : lm_score(p, bm[0].ctx[0], ctx_max < 1 ? ctx_max : 1, (uint32_t)p.sym_word[c]);
+    }
     __syncthreads();
 
     int n = 1, cb = 0, tc = 0, rb = 0;
@@ -504,6 +546,12 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p)
                     NX.wd[r] = X.wd[j];
                     NX.bg[r] = X.bg[j];
                 }
+                if constexpr (NN) {
+                    const uint4* src = (const uint4*)(win[cb] + (size_t)j * WIN);
+                    uint4* dst = (uint4*)(win[cb ^ 1] + (size_t)r * WIN);
+                    dst[0] = src[0];
+                    dst[1] = src[1];
+                }
             } else {
                 NB.h[r] = hstep(B.h[j], c);
                 NB.ph[r] = B.h[j];
@@ -522,6 +570,14 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p)
                     NX.wd[r] = wd;
                     NX.bg[r] = wd >= 0 ? lex_bg(p, pw, wd) : 0.0f;
                 }
+                if constexpr (NN) {
+                    // the parent's window, one slot older, and the new symbol's LM id
+                    const uint8_t* src = win[cb] + (size_t)j * WIN;
+                    uint8_t* dst = win[cb ^ 1] + (size_t)r * WIN;
+                    const int CK = nn.m.K;
+                    for (int s = 0; s + 1 < CK; ++s) dst[s] = src[s + 1];
+                    dst[CK - 1] = (uint8_t)p.sym_word[c];
+                }
             }
             rec[(int64_t)t * K + r] = (j << 16) | c;
         }
@@ -532,7 +588,36 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p)
         if (tid < nsel) htab_insert(nt, NB.h[tid], tid);
 
         // ---- 4. LM rows: carried entries keep theirs, new ones query the LM ----------------
-        if (has_lm) {
+        if constexpr (NN) {
+            for (int it = tid; it < nsel * A; it += NT) {
+                const int r = it / A;
+                const int src = NB.prev[r];
+                if (src >= 0) rows[rb ^ 1][it] = rows[rb][src * A + (it - r * A)];
+            }
+            // the new entries in rank order, 32 to a tile (sel_idx is free until the next select)
+            const int fresh = tid < nsel && NB.prev[tid] < 0;
+            int n_new;
+            const int pos = block_excl_scan(fresh, scan_scratch, &n_new);
+            if (fresh) sel_idx[pos] = tid;
+            __syncthreads();
+            const int CK = nn.m.K, Vp = nn.m.Vp;
+            const uint8_t* wn = win[cb ^ 1];
+            for (int t0 = 0; t0 < n_new; t0 += NN_TILE) {
+                const int cnt = min(NN_TILE, n_new - t0);
+                for (int i = tid; i < cnt * CK; i += NT) {
+                    const int e = i / CK, s = i - e * CK;
+                    nn_ids[i] = wn[(size_t)sel_idx[t0 + e] * WIN + s];
+                }
+                __syncthreads();
+                nnlm_tile(nn.m, nn_ids, cnt, nn_act, nn_rows);
+                for (int i = tid; i < cnt * A; i += NT) {
+                    const int e = i / A, c = i - e * A;
+                    rows[rb ^ 1][sel_idx[t0 + e] * A + c] = c == 0 ? 0.0f : nn_rows[(size_t)e * Vp + p.sym_word[c]];
+                }
+                __syncthreads();
+            }
+            rb ^= 1;
+        } else if (has_lm) {
             for (int it = tid; it < nsel * A; it += NT) {
                 const int r = it / A, c = it - r * A;
                 const int src = NB.prev[r];
@@ -572,9 +657,11 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p)
     }
 }
 
-__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p) { beam_search<false>(p); }
+__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p) { beam_search<false, false>(p, NoNNArgs{}); }
 
-__global__ __launch_bounds__(NT) void ctc_lexbeam_kernel(BeamArgs p) { beam_search<true>(p); }
+__global__ __launch_bounds__(NT) void ctc_lexbeam_kernel(BeamArgs p) { beam_search<true, false>(p, NoNNArgs{}); }
+
+__global__ __launch_bounds__(NT) void ctc_nnbeam_kernel(BeamArgs p, NNArgs nn) { beam_search<false, true>(p, nn); }
 
 struct BeamPlan {
     std::vector<UttDesc> utt;
@@ -582,7 +669,8 @@ struct BeamPlan {
     size_t total = 0;
 };
 
-int plan_beam(const sctc_beam_config* cfg, BeamPlan& pl)
+// nn_extra: bytes per utterance of the neural LM search (windows, one LM tile) on top of the LM rows
+int plan_beam(const sctc_beam_config* cfg, BeamPlan& pl, size_t nn_extra = 0)
 {
     SCTC_CHECK_ARG(cfg, "beam: null config");
     SCTC_CHECK_ARG(cfg->B >= 1, "beam: empty batch");
@@ -601,7 +689,7 @@ int plan_beam(const sctc_beam_config* cfg, BeamPlan& pl)
     }
     const int64_t M = (int64_t)cfg->beam * cfg->A;
     const size_t fixed = al256(2 * M * sizeof(float2)) + al256(M * sizeof(uint64_t)) +
-                         (cfg->lm ? al256(2 * M * sizeof(float)) : 0);
+                         (cfg->lm || nn_extra ? al256(2 * M * sizeof(float)) : 0) + nn_extra;
     pl.utt.resize(cfg->B);
     pl.head = align256(cfg->B * sizeof(UttDesc)) + align256(AMAX * sizeof(int32_t));
     size_t off = pl.head;
@@ -643,6 +731,32 @@ int plan_lexbeam(const sctc_lexbeam_config* cfg, BeamPlan& pl)
     c.alpha = cfg->alpha;
     c.beta = cfg->beta;
     return plan_beam(&c, pl);
+}
+
+// the neural LM search plans like the character search with an LM, plus its windows and LM tile
+int plan_nnbeam(const sctc_nnbeam_config* cfg, BeamPlan& pl)
+{
+    SCTC_CHECK_ARG(cfg, "nnbeam: null config");
+    SCTC_CHECK_ARG(cfg->lm, "nnbeam: null LM");
+    SCTC_CHECK_ARG(cfg->sym_word, "nnbeam: null symbol -> LM id map");
+    SCTC_CHECK_ARG(cfg->A >= 2 && cfg->A <= AMAX, "nnbeam: alphabet size %d outside 2..%d", cfg->A, AMAX);
+    SCTC_CHECK_ARG(cfg->beam >= 1 && cfg->beam <= KMAX, "nnbeam: beam width %d outside 1..%d", cfg->beam, KMAX);
+    const NNLMDev& m = cfg->lm->dev;
+    for (int c = 1; c < cfg->A; ++c)
+        SCTC_CHECK_ARG(cfg->sym_word[c] >= 0 && cfg->sym_word[c] < m.V,
+                       "nnbeam: symbol %d maps to LM id %d outside 0..%d", c, cfg->sym_word[c], m.V - 1);
+    sctc_beam_config c{};
+    c.B = cfg->B;
+    c.A = cfg->A;
+    c.dtype = cfg->dtype;
+    c.beam = cfg->beam;
+    c.nbest = cfg->nbest;
+    c.ld = cfg->ld;
+    c.T_b = cfg->T_b;
+    c.frame_off = cfg->frame_off;
+    c.alpha = cfg->alpha;
+    c.beta = cfg->beta;
+    return plan_beam(&c, pl, al256((size_t)2 * cfg->beam * WIN) + nn_tile_bytes(m.hmax, m.Vp, m.K));
 }
 
 }  // namespace
@@ -897,6 +1011,60 @@ int sctc_ctc_lexbeam_decode_batch(const sctc_lexbeam_config* cfg, const void* pr
     a.lx_start = lx->start;
     a.space = cfg->space;
     hipLaunchKernelGGL(ctc_lexbeam_kernel, dim3(cfg->B), dim3(NT), 0, s, a);
+    SCTC_HIP_TRY(hipGetLastError());
+    return SCTC_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+size_t sctc_ctc_nnbeam_workspace_bytes(const sctc_nnbeam_config* cfg)
+{
+    BeamPlan pl;
+    if (plan_nnbeam(cfg, pl) != SCTC_OK) return 0;
+    return pl.total;
+}
+
+int sctc_ctc_nnbeam_decode_batch(const sctc_nnbeam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                                 int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream)
+{
+    BeamPlan pl;
+    SCTC_TRY(plan_nnbeam(cfg, pl));
+    SCTC_CHECK_ARG(probs_dev && lengths_dev && scores_dev && workspace_dev, "nnbeam: null device pointer");
+    int64_t total_T = 0;
+    for (int b = 0; b < cfg->B; ++b) total_T += cfg->T_b[b];
+    SCTC_CHECK_ARG(ids_dev || total_T == 0, "nnbeam: null ids");
+    if (workspace_bytes < pl.total)
+        return set_error(SCTC_ERR_WORKSPACE, "nnbeam: workspace %zu bytes < %zu needed", workspace_bytes, pl.total);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<char> head(pl.head, 0);
+    memcpy(head.data(), pl.utt.data(), cfg->B * sizeof(UttDesc));
+    const size_t sym_off = align256(cfg->B * sizeof(UttDesc));
+    memcpy(head.data() + sym_off, cfg->sym_word, cfg->A * sizeof(int32_t));
+    ((int32_t*)(head.data() + sym_off))[0] = 0;        // the blank has no LM id; never read
+    SCTC_HIP_TRY(hipMemcpyAsync(workspace_dev, head.data(), pl.head, hipMemcpyHostToDevice, s));
+    SCTC_HIP_TRY(hipStreamSynchronize(s));
+
+    BeamArgs a{};
+    a.probs = probs_dev;
+    a.ld = cfg->ld;
+    a.f64 = cfg->dtype == SCTC_F64;
+    a.A = cfg->A;
+    a.K = cfg->beam;
+    a.nbest = cfg->nbest;
+    a.alpha = cfg->alpha;
+    a.beta = cfg->beta;
+    a.utt = (const UttDesc*)workspace_dev;
+    a.sym_word = (const int32_t*)((char*)workspace_dev + sym_off);
+    a.ws = (char*)workspace_dev;
+    a.ids = ids_dev;
+    a.lens = lengths_dev;
+    a.scores = scores_dev;
+    NNArgs nn{};
+    nn.m = cfg->lm->dev;
+    hipLaunchKernelGGL(ctc_nnbeam_kernel, dim3(cfg->B), dim3(NT), 0, s, a, nn);
     SCTC_HIP_TRY(hipGetLastError());
     return SCTC_OK;
 }

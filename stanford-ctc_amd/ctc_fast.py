@@ -12,7 +12,8 @@ anything else raises ``ValueError`` like the memoryview does.  The float64 host
 signature runs the float64 device kernels.  Additional entry points (not in the
 reference) take batches and device tensors: :func:`ctc_loss_batch`; and the prefix beam
 search decoder of ``ctc_fast/new_decoder/decoder.pyx`` batched over utterances:
-:func:`decode_beam_batch` with an optional character LM (:class:`DecodeLM`).
+:func:`decode_beam_batch` with an optional character LM (an n-gram :class:`DecodeLM` or a
+neural :class:`DecodeNNLM`).
 
 There is no CPU fallback: without the HIP library or without a GPU the calls raise.
 """
@@ -212,6 +213,81 @@ class DecodeLM(object):
             pass
 
 
+class DecodeNNLM(object):
+    """A neural character LM on the device for :func:`decode_beam_batch`: an
+    :class:`nn_lm.NNCharLM` (or the path of its ``.npz``) uploaded once, plus the LM id of every
+    CTC symbol -- ``symbols`` is the decoder's ``int_char_map`` ({symbol id: token}, chars.txt) or
+    an int32 array of LM ids per symbol.  Every symbol 1..A-1 must have an id (ValueError)."""
+
+    def __init__(self, nnlm, symbols, A=None):
+        import nn_lm
+        if not isinstance(nnlm, nn_lm.NNCharLM):
+            nnlm = nn_lm.NNCharLM.load(nnlm)
+        self.nnlm = nnlm
+        self.handle = None
+        if isinstance(symbols, dict):
+            A = int(A) if A is not None else max(symbols) + 1
+            self.sym_words = nnlm.symbol_words(symbols, A)
+        else:
+            self.sym_words = np.ascontiguousarray(symbols, dtype=np.int32)
+            if A is not None:
+                self.sym_words = self.sym_words[:int(A)]
+            bad = [c for c in range(1, self.sym_words.shape[0]) if not 0 <= self.sym_words[c] < nnlm.V]
+            if bad:
+                raise ValueError("DecodeNNLM: symbol %d maps to LM id %d outside the vocabulary"
+                                 % (bad[0], self.sym_words[bad[0]]))
+        widths, ws, bs = nnlm.padded()
+        n = len(ws)
+        _sctc.require_gpu()
+        wp = (ctypes.c_void_p * n)(*[w.ctypes.data for w in ws])
+        bp = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bs])
+        h = ctypes.c_void_p()
+        rc = _sctc.lib().sctc_nnlm_create(nnlm.V, nnlm.context, n, _sctc.i32(widths), wp, bp, nnlm.bos, nnlm.null,
+                                          ctypes.byref(h))
+        _sctc.check(rc, "DecodeNNLM")
+        self.handle = h
+        self.device_bytes = int(_sctc.lib().sctc_nnlm_bytes(h))
+
+    def contexts(self, prefixes):
+        """int32 [n, K]: the LM's window of every prefix (a sequence of CTC symbol ids)"""
+        out = np.empty((len(prefixes), self.nnlm.context), dtype=np.int32)
+        for i, P in enumerate(prefixes):
+            out[i] = self.nnlm.context_ids([self.sym_words[int(s)] for s in P])
+        return out
+
+    def lm_rows(self, contexts):
+        """float32 [n, V]: log10 P(. | context) for int32 [n, K] windows of LM ids"""
+        torch = _sctc.require_gpu()
+        ctx = np.ascontiguousarray(contexts, dtype=np.int32).reshape(-1, self.nnlm.context)
+        if ctx.size and (ctx.min() < 0 or ctx.max() >= self.nnlm.V):
+            raise ValueError("DecodeNNLM: a context id outside the vocabulary")
+        n = ctx.shape[0]
+        dev = torch.from_numpy(ctx).cuda()
+        out = torch.empty((n, self.nnlm.V), dtype=torch.float32, device=dev.device)
+        rc = _sctc.lib().sctc_nnlm_rows(self.handle, dev.data_ptr(), n, out.data_ptr(), _sctc.current_stream_ptr())
+        _sctc.check(rc, "DecodeNNLM.rows")
+        return out.cpu().numpy()
+
+    def rows(self, prefixes):
+        """float32 [n, A] as the search sees them: column 0 is 0, column c is log10 P(symbol c |
+        prefix) for every prefix (a sequence of CTC symbol ids)"""
+        r = self.lm_rows(self.contexts(prefixes))
+        out = r[:, self.sym_words]
+        out[:, 0] = 0.0
+        return np.ascontiguousarray(out)
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            _sctc.lib().sctc_nnlm_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _decode_inputs(logprobs, lengths, what):
     """(host arrays or None, device tensor or None, A, T_b, numpy dtype, sctc dtype) of a decode call"""
     import torch
@@ -283,13 +359,13 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
 
     logprobs: list of (A, T_b) float32/float64 natural-log probability arrays (symbol 0 the
     blank), or a torch device tensor [sum T][A] with ``lengths`` giving T_b.  lm: a
-    :class:`DecodeLM` or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
+    :class:`DecodeLM`, a :class:`DecodeNNLM` or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
     of int32 symbol-id arrays and float64[B]; with nbest > 1 a list of lists and [B, nbest]
     (entries beyond the beam: empty, -inf)."""
     arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, "decode_beam_batch")
     B = len(T_b)
-    if lm is not None and not isinstance(lm, DecodeLM):
-        raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM or None")
+    if lm is not None and not isinstance(lm, (DecodeLM, DecodeNNLM)):
+        raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM or None")
     if lm is not None and lm.sym_words.shape[0] < A:
         raise ValueError("decode_beam_batch: the LM maps %d symbols, the input has %d"
                          % (lm.sym_words.shape[0], A))
@@ -299,6 +375,11 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
     cfg = _sctc.BeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
                            float(alpha), float(beta), lm.handle if lm is not None else None, _sctc.i32(sw))
     L = _sctc.lib()
+    if isinstance(lm, DecodeNNLM):
+        cfg = _sctc.NNBeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
+                                 float(alpha), float(beta), lm.handle, _sctc.i32(sw))
+        return _decode_launch(cfg, L.sctc_ctc_nnbeam_workspace_bytes, L.sctc_ctc_nnbeam_decode_batch, arrs, src, A,
+                              T_b, dt, nbest, "decode_beam_batch")
     return _decode_launch(cfg, L.sctc_ctc_beam_workspace_bytes, L.sctc_ctc_beam_decode_batch, arrs, src, A, T_b,
                           dt, nbest, "decode_beam_batch")
 

@@ -9,7 +9,8 @@ the same classes and calls, decoding on the MI355X through libsctc_hip.so.
 
 ``probs`` is a float64 (A, T) Fortran-ordered array of natural-log probabilities, as the
 ``double[::1,:]`` memoryview accepts; anything else raises like the memoryview does.  The
-LM is an ARPA file read by arpa_lm.py (kenlm is not needed).  ``decode_batch`` (not in
+LM is an ARPA file read by arpa_lm.py (kenlm is not needed), or -- a path ending in ``.npz`` -- the
+neural character LM of nn_lm.py.  ``decode_batch`` (not in
 the reference) decodes a list of utterances in one launch.
 """
 import numpy as np
@@ -91,7 +92,11 @@ class BeamLMDecoder(DecoderBase):
         self._dev = {}
 
     def load_lm(self, lmfile):
-        self.lm = arpa_lm.ArpaLM(lmfile)
+        if str(lmfile).endswith(".npz"):
+            import nn_lm
+            self.lm = nn_lm.NNCharLM.load(lmfile)
+        else:
+            self.lm = arpa_lm.ArpaLM(lmfile)
         self._dev = {}
         return True
 
@@ -101,7 +106,8 @@ class BeamLMDecoder(DecoderBase):
         if self.int_char_map is None:
             raise ValueError("BeamLMDecoder: load_chars first")
         if A not in self._dev:
-            self._dev[A] = ctc_fast.DecodeLM(self.lm, self.int_char_map, A)
+            cls = ctc_fast.DecodeLM if isinstance(self.lm, arpa_lm.ArpaLM) else ctc_fast.DecodeNNLM
+            self._dev[A] = cls(self.lm, self.int_char_map, A)
         return self._dev[A]
 
     def decode(self, probs, beam=40, alpha=1.0, beta=0.0):
