@@ -287,6 +287,48 @@ int sctc_ctc_nnbeam_decode_batch(const sctc_nnbeam_config* cfg, const void* prob
                                  int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
                                  size_t workspace_bytes, void* stream);
 
+/* ---- scoring: ctc_fast/editDistance.py, ctc_fast/swbd-utils/editDist.pyx -----
+ * Added without an ABI version bump (still 6): sctc_edit_distance_workspace_bytes,
+ * sctc_edit_distance_batch. */
+
+/* The Wagner-Fischer table of editDistance.py:14-24 / editDist.pyx:47-58 for P pairs of int32 sequences
+ * a (rows, length n) and b (columns, length m): D[i,0] = i, D[0,j] = j, D[i,j] = D[i-1,j-1] where
+ * a[i-1] == b[j-1], else 1 + min(D[i-1,j], D[i,j-1], D[i-1,j-1]).  The operation of a cell is the first
+ * that holds of MATCH (0: equal symbols), UP (1: D[i-1,j] == D[i,j]-1), LEFT (2: D[i,j-1] == D[i,j]-1),
+ * SUB (3) -- the order of the trace-backs, editDistance.py:29-38 and editDist.pyx:71-91.  The path runs
+ * from (n,m) along the operations until i == 0 or j == 0; the remaining i count as UP and the remaining
+ * j as LEFT (editDistance.py:42-43, editDist.pyx:94-95).
+ *   editDistance.edit_distance(ref, hyp): a = ref, b = hyp; ins = UP, dels = LEFT, subs = SUB, corr = MATCH
+ *   editDist.edit_distance(hyp, ref):     a = hyp, b = ref; dels = UP, ins = LEFT, subs = SUB, eq = MATCH */
+#define SCTC_EDIT_OPS 1   /* also return the path (hyp_corr / ref_corr / errs_by_pos of editDist.pyx:67-106 derive from it) */
+typedef struct sctc_edit_config {
+    int32_t P;              /* pairs, >= 0 */
+    int32_t flags;          /* 0 | SCTC_EDIT_OPS */
+    const int32_t* a_len;   /* host [P], 0..8191 */
+    const int64_t* a_off;   /* host [P]: pair p's a = a_dev[a_off[p] .. + a_len[p]); offsets may repeat (one
+                               reference, many hypotheses) */
+    const int32_t* b_len;   /* host [P], 0..8191 */
+    const int64_t* b_off;   /* host [P] */
+} sctc_edit_config;
+
+/* *bytes: device workspace the batch needs.  0 without SCTC_EDIT_OPS; with it, the 2-bit operation tables
+ * of the pairs too large for on-chip memory, about n * m / 4 bytes each. */
+int sctc_edit_distance_workspace_bytes(const sctc_edit_config* cfg, size_t* bytes);
+
+/* stats_dev [P][5] int32: D[n,m], UP, LEFT, SUB, MATCH of the path (the return values of
+ * editDistance.py:45 in that order).  With SCTC_EDIT_OPS: the operation codes of pair p in FORWARD order
+ * (nearest the start of the sequences first, as editDist.pyx:108 reverses its lists) from
+ * ops_dev[sum_{q<p} (a_len[q] + b_len[q])], ops_len_dev[p] <= a_len[p] + b_len[p] of them; without it
+ * both are NULL.  SCTC_ERR_ARG (no device needed): NULL config, P < 0, a length outside 0..8191, a negative
+ * offset, missing output pointers; SCTC_ERR_WORKSPACE: workspace too small.  P == 0 launches nothing.
+ * Allocates no device memory; the pair descriptors (40 bytes a pair) go through a pinned host buffer that
+ * the calling thread keeps for the life of the process, and the kernel reads them from there.  A call
+ * waits for the previous call of the same thread to have read its descriptors, so it cannot be recorded
+ * into a stream capture (hipGraph). */
+int sctc_edit_distance_batch(const sctc_edit_config* cfg, const int32_t* a_dev, const int32_t* b_dev,
+                             int32_t* stats_dev, int8_t* ops_dev, int32_t* ops_len_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

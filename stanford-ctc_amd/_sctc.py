@@ -71,6 +71,14 @@ class NNBeamConfig(ctypes.Structure):
                 ("sym_word", c_i32p)]
 
 
+class EditConfig(ctypes.Structure):
+    _fields_ = [("P", ctypes.c_int32), ("flags", ctypes.c_int32), ("a_len", c_i32p), ("a_off", c_i64p),
+                ("b_len", c_i32p), ("b_off", c_i64p)]
+
+
+EDIT_OPS = 1
+EDIT_MAX_LEN = 8191
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -111,6 +119,9 @@ PROTOTYPES = {
     "sctc_ctc_nnbeam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(NNBeamConfig)]),
     "sctc_ctc_nnbeam_decode_batch": (ctypes.c_int, [ctypes.POINTER(NNBeamConfig), vp, vp, vp, vp, vp,
                                                     ctypes.c_size_t, vp]),
+    "sctc_edit_distance_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(EditConfig), ctypes.POINTER(ctypes.c_size_t)]),
+    "sctc_edit_distance_batch": (ctypes.c_int, [ctypes.POINTER(EditConfig), vp, vp, vp, vp, vp, vp, ctypes.c_size_t,
+                                                vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),

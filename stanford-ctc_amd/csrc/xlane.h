@@ -48,6 +48,17 @@ __device__ __forceinline__ double lane_shr1(double v)
 #endif
 }
 
+// the integer form (the edit-distance wavefront, edit_distance.hip): lane 0 receives 0
+__device__ __forceinline__ int lane_shr1(int v)
+{
+#ifdef SCTC_SAFE_XLANE
+    int r = __shfl_up(v, 1, 64);
+    return (threadIdx.x & 63) == 0 ? 0 : r;
+#else
+    return dpp_i32<DPP_WAVE_SHR1>(0, v);
+#endif
+}
+
 // Lanes that receive no source add 0.  With every row enabled (ROW_MASK 0xF) that is what bound_ctrl
 // delivers (a shifted-in lane reads 0) and the `old` operand is dead -- no register pair has to be zeroed
 // in front of the move (two v_mov + a hazard nop per stage; it matters where the wave is issue-bound: the

@@ -13,7 +13,9 @@ signature runs the float64 device kernels.  Additional entry points (not in the
 reference) take batches and device tensors: :func:`ctc_loss_batch`; and the prefix beam
 search decoder of ``ctc_fast/new_decoder/decoder.pyx`` batched over utterances:
 :func:`decode_beam_batch` with an optional character LM (an n-gram :class:`DecodeLM` or a
-neural :class:`DecodeNNLM`).
+neural :class:`DecodeNNLM`); and scoring: :func:`edit_distance_batch` (the table and
+trace-back of ``ctc_fast/editDistance.py`` and ``swbd-utils/editDist.pyx`` for many pairs in
+one launch) and :func:`nbest_oracle`.
 
 There is no CPU fallback: without the HIP library or without a GPU the calls raise.
 """
@@ -462,3 +464,123 @@ def decode_lexicon_beam_batch(logprobs, lengths=None, lexicon=None, beam=40, alp
     L = _sctc.lib()
     return _decode_launch(cfg, L.sctc_ctc_lexbeam_workspace_bytes, L.sctc_ctc_lexbeam_decode_batch, arrs, src, A,
                           T_b, dt, nbest, "decode_lexicon_beam_batch")
+
+
+# ---- scoring: edit distance with error counts and alignments ----
+
+OP_MATCH, OP_UP, OP_LEFT, OP_SUB = 0, 1, 2, 3
+
+
+def _edit_seq(seq, what):
+    arr = np.asarray(seq)
+    if arr.size == 0:
+        return np.zeros(0, dtype=np.int32)
+    if arr.ndim != 1 or arr.dtype.kind not in "iub":
+        raise ValueError("%s: every sequence must be a 1-d sequence of integers" % what)
+    if arr.dtype != np.int32:
+        wide = arr.astype(np.int64) if arr.dtype != np.uint64 else arr
+        if wide.max() > 2 ** 31 - 1 or wide.min() < -2 ** 31:
+            raise ValueError("%s: symbol outside the int32 range" % what)
+    if arr.shape[0] > _sctc.EDIT_MAX_LEN:
+        raise ValueError("%s: a sequence of %d symbols, the limit is %d" % (what, arr.shape[0], _sctc.EDIT_MAX_LEN))
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def edit_distance_batch(a_seqs, b_seqs, ops=False, a_index=None):
+    """Edit distance, error counts and (``ops=True``) alignments of many pairs of integer
+    sequences in one launch: the table and trace-back of ``ctc_fast/editDistance.py:14-45``
+    with a = ref, b = hyp, and of ``swbd-utils/editDist.pyx:47-106`` with a = hyp, b = ref.
+
+    a_seqs, b_seqs: lists of integer sequences (any integer dtype, converted to int32, at most
+    8191 symbols each), one pair per position.  With ``a_index`` (one entry per element of
+    b_seqs) pair p is (a_seqs[a_index[p]], b_seqs[p]): every a is uploaded once however many
+    pairs use it (one reference, many hypotheses).
+
+    Returns ``stats``, int32 [P, 5]: distance, UP, LEFT, SUB, MATCH, where UP consumes a symbol
+    of a alone and LEFT one of b alone (editDistance's ins / dels, editDist's dels / ins).  With
+    ``ops=True`` also a list of int8 arrays, the operations of each pair's path from the start
+    of the sequences to their end (OP_MATCH, OP_UP, OP_LEFT, OP_SUB).  One upload, one launch,
+    one read-back; distance-only calls use no device workspace."""
+    what = "edit_distance_batch"
+    a_arr = [_edit_seq(s, what) for s in a_seqs]
+    b_arr = [_edit_seq(s, what) for s in b_seqs]
+    P = len(b_arr)
+    if a_index is None:
+        if len(a_arr) != P:
+            raise ValueError("%s: %d a sequences for %d b sequences" % (what, len(a_arr), P))
+        a_idx = np.arange(P, dtype=np.int64)
+    else:
+        a_idx = np.asarray(a_index, dtype=np.int64).reshape(-1)
+        if a_idx.shape[0] != P or (P and (a_idx.min() < 0 or a_idx.max() >= len(a_arr))):
+            raise ValueError("%s: a_index must name one of the %d a sequences for each of the %d pairs"
+                             % (what, len(a_arr), P))
+    lens_a = np.array([s.shape[0] for s in a_arr], dtype=np.int64)
+    lens_b = np.array([s.shape[0] for s in b_arr], dtype=np.int64)
+    starts_a = np.concatenate([[0], np.cumsum(lens_a)])[:len(a_arr)].astype(np.int64)
+    total_a = int(lens_a.sum())
+    a_len = np.ascontiguousarray(lens_a[a_idx] if P else [], dtype=np.int32)
+    a_off = np.ascontiguousarray(starts_a[a_idx] if P else [], dtype=np.int64)
+    b_len = np.ascontiguousarray(lens_b, dtype=np.int32)
+    b_off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens_b)])[:P], dtype=np.int64)
+    flags = _sctc.EDIT_OPS if ops else 0
+    cfg = _sctc.EditConfig(P, flags, _sctc.i32(a_len), _sctc.i64(a_off), _sctc.i32(b_len), _sctc.i64(b_off))
+    L = _sctc.lib()
+    nbytes = ctypes.c_size_t(0)
+    _sctc.check(L.sctc_edit_distance_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)), what)
+    if P == 0:
+        stats = np.zeros((0, 5), dtype=np.int32)
+        return (stats, []) if ops else stats
+    torch = _sctc.require_gpu()
+    host = np.concatenate(a_arr + b_arr + [np.zeros(1, dtype=np.int32)])
+    dev = torch.from_numpy(host).cuda()
+    path_len = a_len.astype(np.int64) + b_len
+    ops_total = int(path_len.sum()) if ops else 0
+    # one output buffer, one read-back: [P][5] stats | [P] path lengths | the paths
+    out = torch.empty(24 * P + ops_total, dtype=torch.uint8, device=dev.device)
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=dev.device)
+    base = out.data_ptr()
+    rc = L.sctc_edit_distance_batch(ctypes.byref(cfg), dev.data_ptr(), dev.data_ptr() + 4 * total_a, base,
+                                    base + 24 * P if ops else None, base + 20 * P if ops else None,
+                                    ws.data_ptr() if nbytes.value else None, nbytes.value,
+                                    _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    got = out.cpu().numpy()
+    stats = got[:20 * P].view(np.int32).reshape(P, 5).copy()
+    if not ops:
+        return stats
+    lens = got[20 * P:24 * P].view(np.int32)
+    codes = got[24 * P:].view(np.int8)
+    starts = np.concatenate([[0], np.cumsum(path_len)])
+    return stats, [codes[starts[p]:starts[p] + lens[p]].copy() for p in range(P)]
+
+
+def nbest_oracle(refs, nbest_hyps):
+    """Oracle error of n-best lists: for utterance b the hypothesis of ``nbest_hyps[b]`` (the list
+    that ``decode_beam_batch(..., nbest=k)`` returns for it) closest to ``refs[b]``.  An empty
+    hypothesis is a hypothesis like any other; a caller that wants the ranks beyond the beam
+    (empty, score -inf) left out drops them first.  Returns ``(best_index, best_dist,
+    first_dist)``, int32 [B] each: the rank of the closest hypothesis (ties: the lowest rank),
+    its distance, and the distance of rank 0; -1 / -1 / -1 for an utterance without hypotheses.
+    One :func:`edit_distance_batch` call; every reference is uploaded once."""
+    B = len(refs)
+    if len(nbest_hyps) != B:
+        raise ValueError("nbest_oracle: %d references for %d n-best lists" % (B, len(nbest_hyps)))
+    hyps, a_index, count = [], [], []
+    for b, row in enumerate(nbest_hyps):
+        row = list(row)
+        hyps.extend(row)
+        a_index.extend([b] * len(row))
+        count.append(len(row))
+    stats = edit_distance_batch(refs, hyps, a_index=a_index)
+    best_index = np.full(B, -1, dtype=np.int32)
+    best_dist = np.full(B, -1, dtype=np.int32)
+    first_dist = np.full(B, -1, dtype=np.int32)
+    o = 0
+    for b in range(B):
+        if count[b]:
+            d = stats[o:o + count[b], 0]
+            best_index[b] = int(np.argmin(d))      # the first minimum
+            best_dist[b] = d[best_index[b]]
+            first_dist[b] = d[0]
+        o += count[b]
+    return best_index, best_dist, first_dist

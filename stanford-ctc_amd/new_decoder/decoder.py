@@ -115,8 +115,9 @@ class BeamLMDecoder(DecoderBase):
         (hyp, score), = self.decode_batch([probs], beam, alpha, beta)
         return hyp, score
 
-    def decode_batch(self, probs_list, beam=40, alpha=1.0, beta=0.0):
-        """[(hyp, score)] for a list of (A, T) log-probability arrays, one launch"""
+    def decode_batch(self, probs_list, beam=40, alpha=1.0, beta=0.0, nbest=1):
+        """[(hyp, score)] for a list of (A, T) log-probability arrays, one launch; with nbest > 1 a list
+        of nbest (hyp, score) per utterance, best first (ranks beyond the beam: '', -inf)"""
         if int(beam) < 0:
             raise OverflowError("can't convert negative value to unsigned int")
         for p in probs_list:
@@ -124,5 +125,7 @@ class BeamLMDecoder(DecoderBase):
                 raise ValueError("decode_batch: (A, T) arrays expected")
         A = probs_list[0].shape[0]
         ids, scores = ctc_fast.decode_beam_batch(probs_list, beam=beam, alpha=alpha, beta=beta,
-                                                 lm=self._device_lm(A))
+                                                 lm=self._device_lm(A), nbest=nbest)
+        if nbest > 1:
+            return [[(self._string(h), float(s)) for h, s in zip(row, srow)] for row, srow in zip(ids, scores)]
         return [(self._string(h), float(s)) for h, s in zip(ids, scores)]

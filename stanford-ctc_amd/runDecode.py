@@ -2,7 +2,8 @@
 and runDecode.py:41-77): read ``loglikelihoods_N.pk`` (writeLikelihoods.py), ``chars.txt``,
 the alignment file and an ARPA character LM; decode every utterance with the prefix beam
 search on the GPU, in batches; write one hypothesis per line and report the character error
-rate against the alignments (Wagner-Fischer on the host).
+rate against the alignments: one batched edit-distance launch per decode batch
+(ctc_fast.edit_distance_batch).
 
     python runDecode.py --likelihoods loglikelihoods_1.pk --chars chars.txt --alis alis1.txt \\
         --lm text_char.2g.arpa --out hyps.txt [--beam 40 --alpha 1.0 --beta 0.0 --batch 256]
@@ -14,6 +15,11 @@ next to the character error rate (reference words: the alignment split at the sp
 
     python runDecode.py --method bg --likelihoods loglikelihoods_1.pk --chars chars.txt --alis alis1.txt \\
         --words wordlist --word-lm text_word.2g.arpa --out hyps.txt [--specials [noise] [laughter]]
+
+``--errors FILE`` writes ``key dist ins dels subs corr`` for every scored utterance (characters
+against the alignment, the naming of editDistance.py) and adds a line of totals to the summary;
+``--nbest-oracle K`` (character method) decodes K hypotheses per utterance and prints the CER of
+the best of them next to the 1-best CER.
 """
 import argparse
 import os
@@ -24,6 +30,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import ctc_fast  # noqa: E402
+import editDistance  # noqa: E402
 from new_decoder import decoder  # noqa: E402
 from decoder import decoder_utils  # noqa: E402
 
@@ -37,6 +45,37 @@ def edit_distance(ref, hyp):
             cur[j] = min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (ref[i - 1] != hyp[j - 1]))
         prev = cur
     return prev[-1]
+
+
+def score_pairs(refs, hyps):
+    """int32 [P, 5] (dist, ins, dels, subs, corr; editDistance.py naming) of token sequences, one launch"""
+    ids = editDistance._ids(list(refs) + list(hyps))
+    return ctc_fast.edit_distance_batch(ids[:len(refs)], ids[len(refs):])
+
+
+class ErrorLog(object):
+    """--errors FILE: one line per scored utterance and the totals; a context manager, so the file is closed
+    when decoding raises"""
+
+    def __init__(self, path):
+        self.f = open(path, "w") if path else None
+        self.total = np.zeros(5, dtype=np.int64)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.f:
+            self.f.close()
+
+    def add(self, key, stats):
+        self.total += stats
+        if self.f:
+            self.f.write("%s %d %d %d %d %d\n" % ((key,) + tuple(int(v) for v in stats)))
+
+    def summary(self):
+        if self.f:
+            print("errors %d: ins %d, dels %d, subs %d, corr %d" % tuple(int(v) for v in self.total))
 
 
 def load_alis(ali_file, char_file):
@@ -71,30 +110,38 @@ def tokens(hyp, char_int_map):
 
 def decode_bg(a, ll):
     """--method bg: (CER, WER) of the lexicon-constrained word-bigram search"""
-    import ctc_fast
     chars = decoder_utils.load_chars(a.chars)
     alis = load_alis(a.alis, a.chars)
     lex = ctc_fast.DecodeLexicon(a.words, chars, a.word_lm, a.space, specials=a.specials)
     keys = sorted(ll)
     errs = n_ref = werrs = n_words = 0
-    with open(a.out, "w") as out:
+    with open(a.out, "w") as out, ErrorLog(a.errors) as log:
         for g in range(0, len(keys), a.batch):
             ks = keys[g:g + a.batch]
             hyps, scores = ctc_fast.decode_lexicon_beam_batch([np.asarray(ll[k]) for k in ks], lexicon=lex,
                                                               beam=a.beam, alpha=a.alpha, beta=a.beta)
+            scored, refs, cand = [], [], []
             for k, ids, score in zip(ks, hyps, scores):
                 toks = decoder_utils.int_to_char(ids, chars)
-                out.write("%s %.6f %s\n" % (k, score, decoder_utils.collapse_seq(toks, a.space)))
+                words = decoder_utils.collapse_seq(toks, a.space)
+                out.write("%s %.6f %s\n" % (k, score, words))
                 if k in alis:
-                    errs += edit_distance(alis[k], toks)
-                    n_ref += len(alis[k])
-                    ref_words = decoder_utils.collapse_seq(alis[k], a.space).split()
-                    werrs += edit_distance(ref_words, decoder_utils.collapse_seq(toks, a.space).split())
-                    n_words += len(ref_words)
+                    scored.append(k)
+                    refs += [alis[k], decoder_utils.collapse_seq(alis[k], a.space).split()]
+                    cand += [toks, words.split()]
+            # characters and words of the whole decode batch in one launch: pairs 2i and 2i + 1
+            stats = score_pairs(refs, cand)
+            for i, k in enumerate(scored):
+                errs += int(stats[2 * i, 0])
+                n_ref += len(refs[2 * i])
+                werrs += int(stats[2 * i + 1, 0])
+                n_words += len(refs[2 * i + 1])
+                log.add(k, stats[2 * i])
     cer = errs / float(max(n_ref, 1))
     wer = werrs / float(max(n_words, 1))
     print("decoded %d utterances, CER %.4f (%d / %d), WER %.4f (%d / %d)"
           % (len(keys), cer, errs, n_ref, wer, werrs, n_words))
+    log.summary()
     return cer, wer
 
 
@@ -115,7 +162,15 @@ def main(argv=None):
     ap.add_argument("--alpha", type=float, default=1.0)
     ap.add_argument("--beta", type=float, default=0.0)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--errors", help="write `key dist ins dels subs corr` per scored utterance to this file")
+    ap.add_argument("--nbest-oracle", type=int, default=0, metavar="K",
+                    help="also report the CER of the best of K hypotheses per utterance (character method, K <= beam)")
     a = ap.parse_args(argv)
+    K = a.nbest_oracle
+    if K and a.method == "bg":
+        ap.error("--nbest-oracle is for the character method")
+    if K and not 1 <= K <= a.beam:
+        ap.error("--nbest-oracle K needs 1 <= K <= beam")
     with open(a.likelihoods, "rb") as f:
         ll = pickle.load(f)
     if a.method == "bg":
@@ -129,19 +184,39 @@ def main(argv=None):
     dec.load_chars(a.chars)
     dec.load_lm(a.lm)
     keys = sorted(ll)
-    errs = n_ref = 0
-    with open(a.out, "w") as out:
+    errs = n_ref = oracle_errs = 0
+    with open(a.out, "w") as out, ErrorLog(a.errors) as log:
         for g in range(0, len(keys), a.batch):
             ks = keys[g:g + a.batch]
             res = dec.decode_batch([np.asfortranarray(ll[k], dtype=np.float64) for k in ks],
-                                   a.beam, a.alpha, a.beta)
-            for k, (hyp, score) in zip(ks, res):
-                out.write("%s %.6f %s\n" % (k, score, hyp))
+                                   a.beam, a.alpha, a.beta, nbest=max(K, 1))
+            if K <= 1:
+                res = [[r] for r in res]
+            scored, refs, cand, lists = [], [], [], []
+            for k, row in zip(ks, res):
+                out.write("%s %.6f %s\n" % (k, row[0][1], row[0][0]))
                 if k in alis:
-                    errs += edit_distance(alis[k], tokens(hyp, dec.char_int_map))
-                    n_ref += len(alis[k])
+                    scored.append(k)
+                    refs.append(alis[k])
+                    cand.append(tokens(row[0][0], dec.char_int_map))
+                    # ranks beyond the beam (score -inf) are no hypotheses; rank 0 always is
+                    lists.append([cand[-1]] + [tokens(h, dec.char_int_map) for h, s in row[1:] if s > -np.inf])
+            stats = score_pairs(refs, cand)
+            for k, ref, st in zip(scored, refs, stats):
+                errs += int(st[0])
+                n_ref += len(ref)
+                log.add(k, st)
+            if K:
+                table = {}
+                ids = [[table.setdefault(t, len(table)) for t in r] for r in refs]
+                nb = [[[table.setdefault(t, len(table)) for t in h] for h in row] for row in lists]
+                oracle_errs += int(ctc_fast.nbest_oracle(ids, nb)[1].sum()) if ids else 0
     cer = errs / float(max(n_ref, 1))
     print("decoded %d utterances, CER %.4f (%d / %d)" % (len(keys), cer, errs, n_ref))
+    log.summary()
+    if K:
+        print("oracle CER of %d-best %.4f (%d / %d), 1-best CER %.4f (%d / %d)"
+              % (K, oracle_errs / float(max(n_ref, 1)), oracle_errs, n_ref, cer, errs, n_ref))
     return cer
 
 
