@@ -329,6 +329,56 @@ int sctc_edit_distance_batch(const sctc_edit_config* cfg, const int32_t* a_dev, 
                              int32_t* stats_dev, int8_t* ops_dev, int32_t* ops_len_dev, void* workspace_dev,
                              size_t workspace_bytes, void* stream);
 
+/* ---- forced alignment and sentence scoring: the align / refScore of ctc_fast/decoder/decoder_utils.py:64-109 -----
+ * Added without an ABI version bump (still 6): sctc_ctc_align_workspace_bytes, sctc_ctc_align_batch
+ * (DESIGN.md §4.9).  decode() returns (hyp, hypScore, refScore, align); the reference never computed refScore
+ * (decoder_utils.py:68-70) and has an alignment for the pointwise-argmax decoder only, so its CTM writer gives
+ * every word the whole segment's time (swbd-utils/convert_to_ctm.py:27-37). */
+
+/* Input: natural-log probabilities of a packed batch, [sum T][ld], float32 or float64 (the decoders' layout),
+ * -inf allowed; utterance b has T_b[b] rows from row frame_off[b] and the label row l[0..U) =
+ * labels_dev[label_off[b] .. + U_b[b]).  Extended row x[s], s = 0..2U (S = 2U+1): x[2u+1] = l[u], even s the
+ * blank (ctc_fast.pyx:42-76).  All arithmetic is float64; float32 inputs are widened exactly.
+ *   v_0(0) = y_0(blank), v_0(1) = y_0(x[1]), the other states -inf;
+ *   v_t(s) = best(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) if s odd and x[s] != x[s-2]) + y_t(x[s]),  t >= 1;
+ * best takes the largest value, on ties the FIRST of (stay, s-1, s-2); all candidates -inf: -inf, back-pointer
+ * "stay".  The path ends in state S-1 unless v_{T-1}(S-2) is STRICTLY larger.  The Viterbi score is that end
+ * value, a plain chain of float64 additions.  With SCTC_ALIGN_TOTAL the same pass computes a_t(s) with the
+ * max-shifted log-sum-exp in place of best (-inf (+) -inf = -inf, never NaN); the total is
+ * a_{T-1}(S-1) (+) a_{T-1}(S-2) = log P_ctc(l | y).
+ * status: 0 aligned; 1 no alignment of finite score (T < U + repeats, a lattice cut by -inf): scores -inf,
+ * every frame_label and span -1; 2 a label outside [0, A) or equal to the blank: outputs as for 1, nothing
+ * outside the row is read.  T = 0: status 0 with scores 0.0 when U = 0, else status 1. */
+#define SCTC_ALIGN_TOTAL 1   /* also the sum over all alignments */
+typedef struct sctc_align_config {
+    int32_t B;              /* utterances, >= 0 */
+    int32_t A;              /* symbols, >= 1 */
+    int32_t dtype;          /* SCTC_F32 | SCTC_F64 */
+    int32_t blank;          /* in [0, A) */
+    int32_t ld;             /* elements between rows, >= A */
+    int32_t flags;          /* 0 | SCTC_ALIGN_TOTAL */
+    const int32_t* T_b;     /* host [B], >= 0 */
+    const int64_t* frame_off;   /* host [B] */
+    const int32_t* U_b;     /* host [B], 0..4095 */
+    const int64_t* label_off;   /* host [B]; offsets may repeat */
+} sctc_align_config;
+
+/* *bytes: device workspace the batch needs: the 2-bit back-pointers of the utterances too long for on-chip
+ * memory, about T * (2U+1) / 4 bytes each (states rounded up to the launch's width). */
+int sctc_ctc_align_workspace_bytes(const sctc_align_config* cfg, size_t* bytes);
+
+/* frame_label_dev int32 [sum T], at frame_off[b]: the index u of the label a frame is aligned to, -1 for blank.
+ * span_dev int32 [sum U][2], utterance b at sum_{q<b} U_b[q]: first and last frame of label u, inclusive.
+ * scores_dev double [B][2]: Viterbi and total (NaN without SCTC_ALIGN_TOTAL).  status_dev int32 [B].
+ * SCTC_ERR_ARG (no device needed): NULL config or outputs, negative sizes, ld < A, a blank outside [0, A),
+ * U > 4095, negative offsets, unknown dtype or flags; SCTC_ERR_WORKSPACE: workspace too small.  B == 0 launches
+ * nothing.  Allocates no device memory; the utterance descriptors go through the calling thread's pinned host
+ * buffer as those of sctc_edit_distance_batch do (same remark on stream capture).  SCTC_ALIGN_PATH=wave|wide in
+ * the environment forces the kernel (tests, A/B runs); by default the longest label row decides. */
+int sctc_ctc_align_batch(const sctc_align_config* cfg, const void* logprobs_dev, const int32_t* labels_dev,
+                         int32_t* frame_label_dev, int32_t* span_dev, double* scores_dev, int32_t* status_dev,
+                         void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

@@ -79,6 +79,16 @@ class EditConfig(ctypes.Structure):
 EDIT_OPS = 1
 EDIT_MAX_LEN = 8191
 
+
+class AlignConfig(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("A", ctypes.c_int32), ("dtype", ctypes.c_int32), ("blank", ctypes.c_int32),
+                ("ld", ctypes.c_int32), ("flags", ctypes.c_int32), ("T_b", c_i32p), ("frame_off", c_i64p),
+                ("U_b", c_i32p), ("label_off", c_i64p)]
+
+
+ALIGN_TOTAL = 1
+ALIGN_MAX_U = 4095
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -122,6 +132,9 @@ PROTOTYPES = {
     "sctc_edit_distance_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(EditConfig), ctypes.POINTER(ctypes.c_size_t)]),
     "sctc_edit_distance_batch": (ctypes.c_int, [ctypes.POINTER(EditConfig), vp, vp, vp, vp, vp, vp, ctypes.c_size_t,
                                                 vp]),
+    "sctc_ctc_align_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(AlignConfig), ctypes.POINTER(ctypes.c_size_t)]),
+    "sctc_ctc_align_batch": (ctypes.c_int, [ctypes.POINTER(AlignConfig), vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t,
+                                            vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),

@@ -15,7 +15,8 @@ search decoder of ``ctc_fast/new_decoder/decoder.pyx`` batched over utterances:
 :func:`decode_beam_batch` with an optional character LM (an n-gram :class:`DecodeLM` or a
 neural :class:`DecodeNNLM`); and scoring: :func:`edit_distance_batch` (the table and
 trace-back of ``ctc_fast/editDistance.py`` and ``swbd-utils/editDist.pyx`` for many pairs in
-one launch) and :func:`nbest_oracle`.
+one launch), :func:`nbest_oracle`, and the forced alignment :func:`align_batch` with
+:func:`score_sentences` (the ``align`` and ``refScore`` of ``decoder_utils.decode``).
 
 There is no CPU fallback: without the HIP library or without a GPU the calls raise.
 """
@@ -552,6 +553,137 @@ def edit_distance_batch(a_seqs, b_seqs, ops=False, a_index=None):
     codes = got[24 * P:].view(np.int8)
     starts = np.concatenate([[0], np.cumsum(path_len)])
     return stats, [codes[starts[p]:starts[p] + lens[p]].copy() for p in range(P)]
+
+
+# ---- forced alignment and sentence scoring ----
+
+ALIGN_WAVE_MAX_S = 512          # states of the wave path (csrc/ctc_align.hip)
+ALIGN_BP_LDS_BYTES = 64 * 1024  # back-pointers of an utterance stay on chip up to this size
+ALIGN_STAGE_BYTES = 16 * 1024   # otherwise the trace-back stages them through a block of this size
+
+
+def align_plan(U_max, path=None):
+    """How ctc_align.hip runs a batch whose longest label row has ``U_max`` labels (``path``: the
+    value of SCTC_ALIGN_PATH, None = not set): ``path``, states per thread ``spl``, threads ``nl``,
+    frames per back-pointer word ``fpw``, ``lds_frames`` (the largest T whose back-pointers stay on
+    chip) and ``stage_frames`` (frames per staging block of the trace-back beyond that)."""
+    S = 2 * int(U_max) + 1
+    wide = S > ALIGN_WAVE_MAX_S or path == "wide"
+    if wide:
+        spl, nl = 8, max(64, ((S + 7) // 8 + 63) // 64 * 64)
+    else:
+        spl, nl = (1 if S <= 64 else 2 if S <= 128 else 4 if S <= 256 else 8), 64
+    fpw = 16 // spl
+    return {"path": "wide" if wide else "wave", "spl": spl, "nl": nl, "fpw": fpw,
+            "lds_frames": ALIGN_BP_LDS_BYTES // (4 * nl) * fpw, "stage_frames": ALIGN_STAGE_BYTES // (4 * nl) * fpw}
+
+
+def align_batch(logprobs, seqs, lengths=None, blank=0, total=False):
+    """CTC forced alignment of a label row per utterance, batched: the best path
+    of ``seqs[b]`` through the lattice of ctc_fast.pyx:42-76 over utterance b, and with
+    ``total=True`` also log P_ctc(seqs[b] | utterance b), the sum over all of its alignments.
+
+    logprobs: as for :func:`decode_beam_batch` -- a list of (A, T_b) float32/float64 natural-log
+    probability arrays, or a torch device tensor [sum T][A] (any row stride) with ``lengths``.
+    seqs: one integer sequence per utterance, at most 4095 labels.  Returns (frame_label, spans,
+    viterbi, total, status): a list of int32 [T_b] (the index u of the label a frame is aligned to,
+    -1 for blank), a list of int32 [U_b, 2] (first and last frame of label u, inclusive), float64
+    [B], float64 [B] or None, int32 [B] (0 aligned; 1 no alignment of finite score; 2 a label
+    outside [0, A) or equal to the blank; then the scores are -inf and the rest -1)."""
+    what = "align_batch"
+    arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, what)
+    B = len(T_b)
+    if len(seqs) != B:
+        raise ValueError("%s: %d label rows for %d utterances" % (what, len(seqs), B))
+    for s in seqs:
+        if len(s) > _sctc.ALIGN_MAX_U:
+            raise ValueError("%s: a label row of %d labels, the limit is %d" % (what, len(s), _sctc.ALIGN_MAX_U))
+    labs = [_edit_seq(s, what) for s in seqs]
+    U_b = np.ascontiguousarray([s.shape[0] for s in labs], dtype=np.int32)
+    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(T_b)[:-1]]) if B else [], dtype=np.int64)
+    loff = np.ascontiguousarray(np.concatenate([[0], np.cumsum(U_b)[:-1]]) if B else [], dtype=np.int64)
+    ld = int(A)
+    if src is not None:     # rows of a wider tensor are read in place (ld > A)
+        dev = src if src.stride(1) == 1 and A <= src.stride(0) < 2 ** 31 else src.contiguous()
+        ld = int(dev.stride(0))
+    flags = _sctc.ALIGN_TOTAL if total else 0
+    cfg = _sctc.AlignConfig(B, int(A), dtype, int(blank), ld, flags, _sctc.i32(Tb), _sctc.i64(off), _sctc.i32(U_b),
+                            _sctc.i64(loff))
+    L = _sctc.lib()
+    nbytes = ctypes.c_size_t(0)
+    _sctc.check(L.sctc_ctc_align_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)), what)
+    torch = _sctc.require_gpu()
+    if src is None:
+        host = np.concatenate([np.ascontiguousarray(p.T, dtype=dt) for p in arrs], axis=0) if sum(T_b) else \
+            np.zeros((1, A), dtype=dt)
+        dev = torch.from_numpy(host).cuda()
+    sum_T, sum_U = int(Tb.sum()), int(U_b.sum())
+    labels = torch.from_numpy(np.concatenate(labs + [np.zeros(1, dtype=np.int32)])).to(dev.device)
+    # one output buffer, one read-back: [B][2] scores | [B] status | frame labels | spans
+    o_status, o_fl, o_span = 16 * B, 20 * B, 20 * B + 4 * sum_T
+    out = torch.empty(o_span + 8 * sum_U + 8, dtype=torch.uint8, device=dev.device)
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=dev.device)
+    base = out.data_ptr()
+    rc = L.sctc_ctc_align_batch(ctypes.byref(cfg), dev.data_ptr(), labels.data_ptr(), base + o_fl, base + o_span, base,
+                                base + o_status, ws.data_ptr() if nbytes.value else None, nbytes.value,
+                                _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    got = out.cpu().numpy()
+    scores = got[:o_status].view(np.float64).reshape(B, 2)
+    status = got[o_status:o_fl].view(np.int32).copy()
+    fl = got[o_fl:o_span].view(np.int32)
+    span = got[o_span:o_span + 8 * sum_U].view(np.int32).reshape(sum_U, 2)
+    frame_label = [fl[o:o + t].copy() for o, t in zip(off, T_b)]
+    spans = [span[o:o + u].copy() for o, u in zip(loff, U_b)]
+    return frame_label, spans, scores[:, 0].copy(), scores[:, 1].copy() if total else None, status
+
+
+def lm_sentence_scores(seqs, lm):
+    """float64 [B]: sum_i log10 P_LM(l_i | <s>, l_<i) of every label row under ``lm`` (a :class:`DecodeLM`
+    or a :class:`DecodeNNLM`), the float32 values that the beam search adds, summed in float64; no
+    end-of-sentence term.  An n-gram LM is scored on the host (``ArpaLM.score_ids``), the neural LM by
+    one ``DecodeNNLM.rows`` call over all prefixes."""
+    out = np.zeros(len(seqs), dtype=np.float64)
+    if isinstance(lm, DecodeLM):
+        for b, s in enumerate(seqs):
+            ctx = [lm.arpa.bos]
+            for c in s:
+                w = int(lm.sym_words[int(c)])
+                out[b] += float(lm.arpa.score_ids(ctx, w))
+                ctx.append(w)
+        return out
+    if not isinstance(lm, DecodeNNLM):
+        raise ValueError("lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM or None")
+    prefixes = [tuple(int(c) for c in s[:i]) for s in seqs for i in range(len(s))]
+    if prefixes:
+        rows = lm.rows(prefixes)
+        k = 0
+        for b, s in enumerate(seqs):
+            for c in s:
+                out[b] += float(rows[k, int(c)])
+                k += 1
+    return out
+
+
+def score_sentences(logprobs, seqs, lengths=None, lm=None, alpha=1.0, beta=0.0):
+    """float64 [B]: the score of label row ``seqs[b]`` under the objective that the character beam
+    search maximises, log P_ctc(l) + alpha * sum_i log10 P_LM(l_i | <s>, l_<i) + beta * U: what the
+    key of :func:`decode_beam_batch` converges to for prefix l with nothing pruned.
+    No end-of-sentence term, as in ``BeamLMDecoder``.  -inf where the row cannot be aligned
+    (status != 0 of :func:`align_batch`).  One :func:`align_batch` call; the LM term is computed on
+    the host (:func:`lm_sentence_scores`)."""
+    rows = [np.asarray(s).reshape(-1) for s in seqs]
+    _, _, _, total, status = align_batch(logprobs, rows, lengths=lengths, total=True)
+    score = np.full(len(rows), -np.inf, dtype=np.float64)
+    ok = status == 0
+    if lm is not None and not isinstance(lm, (DecodeLM, DecodeNNLM)):
+        raise ValueError("score_sentences: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM or None")
+    good = [r if o else r[:0] for r, o in zip(rows, ok)]
+    lmv = lm_sentence_scores(good, lm) if lm is not None else np.zeros(len(rows))
+    for b in np.nonzero(ok)[0]:
+        score[b] = total[b] + float(alpha) * lmv[b] + float(beta) * len(rows[b])
+    return score
 
 
 def nbest_oracle(refs, nbest_hyps):

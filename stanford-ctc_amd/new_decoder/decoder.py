@@ -129,3 +129,18 @@ class BeamLMDecoder(DecoderBase):
         if nbest > 1:
             return [[(self._string(h), float(s)) for h, s in zip(row, srow)] for row, srow in zip(ids, scores)]
         return [(self._string(h), float(s)) for h, s in zip(ids, scores)]
+
+    def score(self, probs, label_ids, alpha=1.0, beta=0.0):
+        """The score of the symbol-id row ``label_ids`` under the objective that :meth:`decode`
+        maximises (``ctc_fast.score_sentences``): the refScore that
+        decoder_utils.py:68-70 left open.  -inf when the row cannot be aligned to ``probs``."""
+        _check_probs(probs)
+        return float(ctc_fast.score_sentences([probs], [label_ids], lm=self._device_lm(probs.shape[0]),
+                                              alpha=alpha, beta=beta)[0])
+
+    def align(self, probs, label_ids):
+        """The best alignment of ``label_ids`` to ``probs`` (``ctc_fast.align_batch``): (frame_label
+        int32 [T], spans int32 [U, 2], viterbi score, status)."""
+        _check_probs(probs)
+        fl, spans, vit, _, status = ctc_fast.align_batch([probs], [label_ids])
+        return fl[0], spans[0], float(vit[0]), int(status[0])

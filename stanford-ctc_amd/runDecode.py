@@ -20,6 +20,14 @@ next to the character error rate (reference words: the alignment split at the sp
 against the alignment, the naming of editDistance.py) and adds a line of totals to the summary;
 ``--nbest-oracle K`` (character method) decodes K hypotheses per utterance and prints the CER of
 the best of them next to the 1-best CER.
+
+``--ref-scores FILE`` (character method) writes ``key hypscore refscore`` per utterance with a
+transcript: the transcript scored under the objective the search maximises
+(ctc_fast.score_sentences; the refScore that the reference's decoder_utils.py:68-70
+left open), and adds a line that counts the search errors (refscore > hypscore) and the transcripts
+that cannot be aligned.  ``--ctm FILE [--frame-shift 0.01]`` writes the 1-best hypotheses as a CTM
+(swbd-utils/convert_to_ctm.py:21-37) with the time of every word taken from the forced alignment of
+the hypothesis (ctc_fast.align_batch): words are the runs of labels between ``--space`` symbols.
 """
 import argparse
 import os
@@ -76,6 +84,73 @@ class ErrorLog(object):
     def summary(self):
         if self.f:
             print("errors %d: ins %d, dels %d, subs %d, corr %d" % tuple(int(v) for v in self.total))
+
+
+class RefScoreLog(object):
+    """--ref-scores FILE: ``key hypscore refscore`` per utterance with a transcript; counts the search errors
+    (the transcript scores higher than the hypothesis that the search returned) and the transcripts that
+    cannot be aligned"""
+
+    def __init__(self, path):
+        self.f = open(path, "w") if path else None
+        self.n = self.search_errors = self.unaligned = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.f:
+            self.f.close()
+
+    def add(self, key, hyp_score, ref_score):
+        self.n += 1
+        self.search_errors += int(ref_score > hyp_score)
+        self.unaligned += int(ref_score == -np.inf)
+        self.f.write("%s %.6f %.6f\n" % (key, hyp_score, ref_score))
+
+    def summary(self):
+        if self.f:
+            print("ref scores of %d transcripts: %d search errors (refscore > hypscore), %d without an alignment"
+                  % (self.n, self.search_errors, self.unaligned))
+
+
+CTM_FORM = "%s %s %0.2f %0.2f %s\n"     # convert_to_ctm.py:21
+
+
+def parse_ctm_key(key):
+    """(file id, channel, segment offset in seconds) of an utterance key, convert_to_ctm.py:27-34: the third
+    ``_`` field is ``start-end`` in centiseconds, the file id the first seven characters, the channel A where
+    the key holds ``-a_``, else B.  A key that does not parse that way: (key, 'A', 0.0)."""
+    try:
+        times = key.split("_")[2]
+        start, _end = [int(x) / 100.0 for x in times.split("-")]
+    except (IndexError, ValueError):
+        return key, "A", 0.0
+    return key[0:7], "A" if "-a_" in key else "B", start
+
+
+def ctm_words(ids, spans, space_id, int_char_map):
+    """[(word, first frame, last frame)]: the maximal runs of labels between space symbols, with the first
+    frame of the first label and the last frame of the last one (inclusive); none for a row without an alignment"""
+    out, run = [], []
+    if len(ids) and np.asarray(spans).min() < 0:    # no alignment (status != 0): no times to give
+        return out
+    for u, c in enumerate(list(ids) + [space_id]):
+        if c == space_id or u == len(ids):
+            if run:
+                out.append(("".join(int_char_map[int(ids[i])] for i in run), int(spans[run[0]][0]), int(spans[run[-1]][1])))
+            run = []
+        else:
+            run.append(u)
+    return out
+
+
+def ctm_lines(key, words, frame_shift):
+    """the CTM lines of one utterance: start = segment offset + first frame * shift, duration = (last frame
+    + 1 - first frame) * shift"""
+    file_id, channel, offset = parse_ctm_key(key)
+    return [CTM_FORM % (file_id, channel, offset + first * frame_shift, (last + 1 - first) * frame_shift, w)
+            for w, first, last in words]
 
 
 def load_alis(ali_file, char_file):
@@ -165,10 +240,19 @@ def main(argv=None):
     ap.add_argument("--errors", help="write `key dist ins dels subs corr` per scored utterance to this file")
     ap.add_argument("--nbest-oracle", type=int, default=0, metavar="K",
                     help="also report the CER of the best of K hypotheses per utterance (character method, K <= beam)")
+    ap.add_argument("--ref-scores", metavar="FILE",
+                    help="write `key hypscore refscore` per utterance with a transcript: the transcript scored under "
+                         "the search's own objective (character method)")
+    ap.add_argument("--ctm", metavar="FILE",
+                    help="write a CTM with the time of every word of the 1-best hypotheses, from their forced "
+                         "alignment (character method)")
+    ap.add_argument("--frame-shift", type=float, default=0.01, help="seconds per frame (--ctm)")
     a = ap.parse_args(argv)
     K = a.nbest_oracle
     if K and a.method == "bg":
         ap.error("--nbest-oracle is for the character method")
+    if (a.ref_scores or a.ctm) and a.method == "bg":
+        ap.error("--ref-scores and --ctm are for the character method")
     if K and not 1 <= K <= a.beam:
         ap.error("--nbest-oracle K needs 1 <= K <= beam")
     with open(a.likelihoods, "rb") as f:
@@ -185,13 +269,28 @@ def main(argv=None):
     dec.load_lm(a.lm)
     keys = sorted(ll)
     errs = n_ref = oracle_errs = 0
-    with open(a.out, "w") as out, ErrorLog(a.errors) as log:
+    space_id = dec.char_int_map.get(a.space)
+    with open(a.out, "w") as out, ErrorLog(a.errors) as log, RefScoreLog(a.ref_scores) as ref_log, \
+            open(a.ctm or os.devnull, "w") as ctm:
         for g in range(0, len(keys), a.batch):
             ks = keys[g:g + a.batch]
-            res = dec.decode_batch([np.asfortranarray(ll[k], dtype=np.float64) for k in ks],
-                                   a.beam, a.alpha, a.beta, nbest=max(K, 1))
+            probs = [np.asfortranarray(ll[k], dtype=np.float64) for k in ks]
+            res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, 1))
             if K <= 1:
                 res = [[r] for r in res]
+            if ref_log.f:       # the transcripts of the batch under the search's objective, one call
+                idx = [i for i, k in enumerate(ks) if k in alis]
+                ref_ids = [[dec.char_int_map.get(t, -1) for t in alis[ks[i]]] for i in idx]
+                if idx:
+                    ref_scores = ctc_fast.score_sentences([probs[i] for i in idx], ref_ids, alpha=a.alpha, beta=a.beta,
+                                                          lm=dec._device_lm(probs[0].shape[0]))
+                    for i, rs in zip(idx, ref_scores):
+                        ref_log.add(ks[i], res[i][0][1], rs)
+            if a.ctm:           # every 1-best hypothesis aligned to its own utterance, one call
+                hyp_ids = [[dec.char_int_map[t] for t in tokens(row[0][0], dec.char_int_map)] for row in res]
+                _, spans, _, _, _ = ctc_fast.align_batch(probs, hyp_ids)
+                for k, ids, sp in zip(ks, hyp_ids, spans):
+                    ctm.writelines(ctm_lines(k, ctm_words(ids, sp, space_id, dec.int_char_map), a.frame_shift))
             scored, refs, cand, lists = [], [], [], []
             for k, row in zip(ks, res):
                 out.write("%s %.6f %s\n" % (k, row[0][1], row[0][0]))
@@ -214,6 +313,7 @@ def main(argv=None):
     cer = errs / float(max(n_ref, 1))
     print("decoded %d utterances, CER %.4f (%d / %d)" % (len(keys), cer, errs, n_ref))
     log.summary()
+    ref_log.summary()
     if K:
         print("oracle CER of %d-best %.4f (%d / %d), 1-best CER %.4f (%d / %d)"
               % (K, oracle_errs / float(max(n_ref, 1)), oracle_errs, n_ref, cer, errs, n_ref))
