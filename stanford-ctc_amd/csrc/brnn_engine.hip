@@ -118,7 +118,7 @@ struct sctc_brnn {
     int rec_sync_mode = 0;
     bool fuse_add = true;      // env SCTC_FUSE_ADD=0: the two sums around the temporal layer by add_kernel (A/B, bit-identity tests)
     int rec_poll_delay = -1;   // env SCTC_REC_POLL_DELAY (s_sleep units before a step's first poll; default by layer size)
-    int rec_variant = 0;   // env SCTC_REC_VARIANT: 1 forces the one-workgroup-per-CU recurrent kernel, 3 the per-step fallback
+    int rec_variant = REC_V_AUTO;   // env SCTC_REC_VARIANT: a RecVariant (recurrent_plan.h)
     int rec_force_fallback = 0;   // set while a timed-out step is retried on the per-step fallback
     int rec_path[2] = {0, 0};     // REC_PATH_* of the last forward / BPTT recurrence
     int rec_retries = 0;          // steps of this handle that were re-run after SCTC_ERR_TIMEOUT
@@ -553,7 +553,7 @@ static int run_forward(sctc_brnn* h, const sctc_minibatch* mb, hipStream_t s, Ph
             r.n_xrows = (int)h->n_xrows;
             r.counters = h->counters;
             r.sync_mode = h->rec_sync_mode;
-            r.variant = h->rec_force_fallback ? 3 : h->rec_variant;
+            r.variant = h->rec_force_fallback ? REC_V_FALLBACK : h->rec_variant;
             r.poll_delay = h->rec_poll_delay;
             r.debug = h->rec_debug_on ? h->rec_debug : nullptr;
             r.prec16 = h->cfg.operand_dtype == SCTC_F16;
@@ -815,7 +815,7 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
             r.n_xrows = (int)h->n_xrows;
             r.counters = h->counters;
             r.sync_mode = h->rec_sync_mode;
-            r.variant = h->rec_force_fallback ? 3 : h->rec_variant;
+            r.variant = h->rec_force_fallback ? REC_V_FALLBACK : h->rec_variant;
             r.poll_delay = h->rec_poll_delay;
             r.debug = h->rec_debug_on ? h->rec_debug + REC_DEBUG_WORDS : nullptr;
             r.prec16 = h->cfg.operand_dtype == SCTC_F16;
@@ -980,7 +980,7 @@ int sctc_brnn_create(const sctc_brnn_config* cfg, float* params_dev, float* grad
     const char* sm = getenv("SCTC_REC_SYNC");
     h->rec_sync_mode = sm ? atoi(sm) : 1;
     const char* rv = getenv("SCTC_REC_VARIANT");
-    h->rec_variant = rv ? atoi(rv) : 0;
+    h->rec_variant = rv ? atoi(rv) : REC_V_AUTO;
     const char* pd = getenv("SCTC_REC_POLL_DELAY");
     h->rec_poll_delay = pd ? atoi(pd) : -1;
     if (const char* fa = getenv("SCTC_FUSE_ADD")) h->fuse_add = atoi(fa) != 0;

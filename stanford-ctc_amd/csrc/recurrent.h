@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "recurrent_plan.h"
+
 namespace sctc {
 
 // Two independent recurrences ("groups") run in one launch on disjoint CUs:
@@ -38,28 +40,13 @@ struct RecArgs {
     int32_t sync_mode;      // 0: plain exchange stores + agent-scope release fence before the flag
                             // 1: write-through (sc1) exchange stores, no fence
     int32_t poll_delay;     // s_sleep units (64 cycles) before the first poll of a step; < 0: pick by layer size
-    int32_t variant;        // 0: pick automatically; 1: force the one-workgroup-per-CU kernel;
-                            // 2: two-chain kernel with the linear (not XCD-grouped) block map;
-                            // 3: force the non-persistent per-step fallback;
-                            // 4: two workgroups per CU for 17..32 utterances (round 1-3 kernel);
-                            // 8..23: both chains in one 8-wave workgroup, mode = variant - 8;
-                            // 40: more than 32 utterances without the load / MFMA pipelining of round 5;
-                            // 42: 6..16 utterances (fp32) on the sentinel / MFMA kernel instead of the single-chain flag kernel;
-                            // 45: 33..48 utterances as ONE launch of the one-workgroup-per-CU kernel (default: 32 + rest);
-                            // 43: the sentinel / VALU kernel for up to 8 utterances (default: up to 3); 44: the single-chain
-                            //     flag kernel from 1 utterance (default: from 4)
-                            // 46: exchange tiles row-major throughout (rounds 1-5a; bit-identical A/B of the lane-order layout);
-                            // 47: more than 32 utterances on the one-slab-per-CU kernel of rounds 1-5 (default since round 6 at 1824 / 2048
-                            //     units: units x utterances, brnn_recurrent_t_kernel); 50: the tiled kernel at 512 / 1024 units as well
-                            //     (no faster there; tests); 49: DIAGNOSTIC, wrong results -- the tiled kernel re-reads step 0's exchange rows
-                            // 51: 17..32 utterances on the two-chain kernel brnn_recurrent_q_kernel (the default up to round 6;
-                            //     since round 7 at 1824 / 2048 units and fp32: the tiled kernel, 16 units x both tiles per CU)
+    int32_t variant;        // a RecVariant (recurrent_plan.h): kernel selection overrides, A/Bs, diagnostics
     unsigned* debug;        // nullable: s_memtime stamps [2 wgs][16 steps][8] for steps 64..79
     int32_t b_off;          // rank of this launch's first utterance in the packed minibatch (minibatches of
                             // more than 128 utterances run as several launches; T_b already points at it)
     const int32_t* T_host;  // nullable: host copy of the full (sorted) T_b, used to shorten later launches
     int32_t linear_map;     // two-chain kernel: linear block -> (chain, producer) map, chain = direction (the single-chain launch of
-                            // 4..16 utterances; set by the launcher -- `variant` keeps its A/B meaning, e.g. 46, there too)
+                            // 4..16 utterances; set by the launcher -- `variant` keeps its A/B meaning, e.g. REC_V_ROW_MAJOR, there too)
     int32_t prec16;         // != 0: "fp16 activations" -- the 6..16-utterance kernel exchanges the state
                             // and holds the weights in 16 bit (float16 forward, bfloat16 BPTT), fp32 accumulate
 };

@@ -56,6 +56,7 @@
 namespace sctc {
 
 typedef void (*RecKernel)(RecArgs);
+static constexpr int REC_THREADS = 256;     // every persistent kernel: four waves
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -124,7 +125,7 @@ __device__ __forceinline__ float4 step_result(const float4& pre, const float4& s
 // uT: the lengths of the tile's utterances, lane uj = utterance uj (0 beyond the minibatch); tile: launch-local index.
 __device__ __forceinline__ int lane_order_steps(int uT, int tile, int b_off, int variant)
 {
-    if (variant == 46) return 0;        // row-major throughout (rounds 1-5a; bit-identical A/B)
+    if (variant == REC_V_ROW_MAJOR) return 0;        // row-major throughout (rounds 1-5a; bit-identical A/B)
     return (tile == 0 && b_off == 0) ? __builtin_amdgcn_readlane(uT, 12) : __builtin_amdgcn_readlane(uT, 0);
 }
 
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_kernel(RecArgs p)
     // Which K half adds the other's partial sums to its own and stores the step's result of tile i.  Rounds 1-4: the
     // lower half, every tile (the upper half's waves sat out the epilogue: 1.8 us of a 128-utterance step).  Round 5:
     // the halves take alternate tiles -- own + other is the same float addition either way round, bit-identical.
-    const bool split_epilogue = NTW >= 2 && p.variant != 40;
+    const bool split_epilogue = NTW >= 2 && p.variant != REC_V_NO_PIPE;
     auto finishes = [&](int i) -> bool { return split_epilogue ? ((i & 1) == kh) : (kh == 0); };
 
     const int dbg_sel = (p.debug && g == 0 && tid == 0) ? (wg == 0 ? 0 : (wg == nwg - 1 ? 1 : -1)) : -1;
@@ -470,7 +471,7 @@ __global__ __launch_bounds__(256, 2) void brnn_recurrent_q_kernel(RecArgs p)
     // workgroups that land on one CU (k and k+32 of an XCD) still belong to different chains.
     // Placement only affects speed: any block -> XCD assignment gives the same results.
     int chain, wg;
-    if (p.variant != 2 && !p.linear_map) {
+    if (p.variant != REC_V_Q_LINEAR && !p.linear_map) {
         const int x = blockIdx.x & 7, k = blockIdx.x >> 3, P = nwg >> 1;   // P blocks per XCD
         const int gx = x >> 2, xl = x & 3;
         const int n0_even = (P + 1) >> 1, n0_odd = P >> 1;                  // chain-0 share per XCD
@@ -564,7 +565,7 @@ __global__ __launch_bounds__(256, 2) void brnn_recurrent_q_kernel(RecArgs p)
 
     // variants 5 / 6 / 7: static issue priority by direction / tile / chain parity (which two chains
     // share a CU is the dispatcher's choice: with the XCD-grouped map the two directions of one tile)
-    if ((p.variant == 5 && g == 0) || (p.variant == 6 && tile == 0) || (p.variant == 7 && ((g ^ tile) & 1) == 0))
+    if ((p.variant == REC_V_Q_PRIO_DIR && g == 0) || (p.variant == REC_V_Q_PRIO_TILE && tile == 0) || (p.variant == REC_V_Q_PRIO_PARITY && ((g ^ tile) & 1) == 0))
         __builtin_amdgcn_s_setprio(3);
     // rowbase / xbase of a step are fetched one step ahead: three dependent L2 round trips at
     // the head of every step would otherwise sit on the recurrence's critical path
@@ -857,7 +858,7 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
             xin[i] = prow * 64u + (unsigned)kq * 16u;
             if (j > 0 && j <= S.tile_T[i] && active)       // the tile was complete at step j - 1: lane order
                 xin[i] = (xb_prev + S.trow[i]) * 64u + (unsigned)lane * 16u;
-            if (p.variant == 49) xin[i] = (unsigned)lane * 16u;     // DIAGNOSTIC (wrong results): every load re-reads step 0's rows -- lines that stay cached -- to time the kernel without the arrival of fresh exchange data
+            if (p.variant == REC_V_T_STALE) xin[i] = (unsigned)lane * 16u;     // DIAGNOSTIC (wrong results): every load re-reads step 0's rows -- lines that stay cached -- to time the kernel without the arrival of fresh exchange data
         }
     };
     // batch bi of a phase into ring slot bi % R
@@ -1234,10 +1235,6 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
 #endif
 }
 
-#ifdef SCTC_REC_EXPERIMENTS    // measured slower / superseded kernels, kept for the A/Bs of profiles/r04_recurrence_q8.md and r05 (build with -DSCTC_REC_EXPERIMENTS)
-#include "recurrent_experiments_q8.inc"
-#endif  // SCTC_REC_EXPERIMENTS
-
 // ---------------------------------------------------------------------------------------
 // Small-batch variant (1..4 utterances: the reference's minibatch-1 mode).  With one utterance
 // a step is a 16 x H matrix-vector product per workgroup (0.1 us of VALU work) and the whole
@@ -1427,12 +1424,8 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_s_kernel(RecArgs p)
     }
 }
 
-#ifdef SCTC_REC_EXPERIMENTS    // superseded at 6..16 utterances by the single-chain flag kernel (round 5); SCTC_REC_VARIANT=42
-#include "recurrent_experiments_m.inc"
-#endif  // SCTC_REC_EXPERIMENTS
-
 // ---------------------------------------------------------------------------------------
-// 16-bit-operand variant of the mid-batch kernel for the "fp16 activations" configuration
+// 16-bit-operand sentinel / MFMA kernel for the "fp16 activations" configuration
 // (BASELINE configs[4]; 6..16 utterances, e.g. cfg-5 with minibatch 8): the recurrent weights
 // and the exchanged state are rounded to 16 bit (float16 in the forward pass, bfloat16 in BPTT:
 // deltas need fp32's exponent range), products are exact and accumulate in fp32 on
@@ -1732,30 +1725,40 @@ int recurrent_supported(int Hp, int B, char* why, int why_len)
     return 1;  // any layer size: grids beyond the device run on the per-step fallback
 }
 
-template <int NTW>
-static RecKernel pick_kernel(int nch_half, bool pipe)
+// Every instantiation the library has, named once: (family, template arguments) of a plan's candidate -> kernel.
+// Per layer size <NCQ, NREG, NK, NCH> of its row in REC_SIZES (recurrent_plan.h).
+#define SCTC_REC_KERNELS_OF_SIZE(X, NCQ, NREG, NK, NCH)                                                         \
+    X(REC_FAM_Q, brnn_recurrent_q_kernel, NCQ, NREG)                                                            \
+    X(REC_FAM_S, brnn_recurrent_s_kernel, NK, 4) X(REC_FAM_S, brnn_recurrent_s_kernel, NK, 8)                   \
+    X(REC_FAM_MH, brnn_recurrent_mh_kernel, NCH, false) X(REC_FAM_MH, brnn_recurrent_mh_kernel, NCH, true)      \
+    X(REC_FAM_SLAB, brnn_recurrent_kernel, 1, NK, false) X(REC_FAM_SLAB, brnn_recurrent_kernel, 2, NK, false)   \
+    X(REC_FAM_SLAB, brnn_recurrent_kernel, 4, NK, false) X(REC_FAM_SLAB, brnn_recurrent_kernel, 4, NK, true)
+#define SCTC_REC_T(X, ...) X(REC_FAM_T, brnn_recurrent_t_kernel, __VA_ARGS__)
+#define SCTC_REC_KERNELS(X)                                                                                     \
+    SCTC_REC_KERNELS_OF_SIZE(X, 8, 0, 16, 4) SCTC_REC_KERNELS_OF_SIZE(X, 16, 0, 32, 8)     /* H = 512, 1024 */  \
+    SCTC_REC_KERNELS_OF_SIZE(X, 29, 10, 57, 15) SCTC_REC_KERNELS_OF_SIZE(X, 32, 13, 64, 16) /* H = 1824, 2048 */ \
+    X(REC_FAM_SLAB, brnn_recurrent_kernel, 1, 0, false) X(REC_FAM_SLAB, brnn_recurrent_kernel, 2, 0, false)     \
+    X(REC_FAM_SLAB, brnn_recurrent_kernel, 4, 0, false)                                    /* any layer size */ \
+    SCTC_REC_T(X, 29, 29, 1, 8, 4, 1, 5, 1) SCTC_REC_T(X, 29, 29, 1, 6, 3, 1, 4, 1) SCTC_REC_T(X, 29, 0, 1, 8, 4, 1, 5, 1) \
+    SCTC_REC_T(X, 32, 32, 1, 8, 4, 1, 5, 1) SCTC_REC_T(X, 32, 32, 1, 6, 3, 1, 4, 1) SCTC_REC_T(X, 32, 0, 1, 8, 4, 1, 5, 1) \
+    SCTC_REC_T(X, 8, 0, 1, 4, 2, 0, 3, 2) SCTC_REC_T(X, 8, 0, 2, 4, 2, 0, 3, 2)                                 \
+    SCTC_REC_T(X, 16, 0, 1, 4, 2, 1, 3, 2) SCTC_REC_T(X, 16, 0, 2, 4, 2, 1, 3, 2)                               \
+    SCTC_REC_T(X, 29, 25, 1, 8, 4, 1, 5, 2) SCTC_REC_T(X, 29, 25, 1, 6, 3, 1, 4, 2) SCTC_REC_T(X, 29, 25, 1, 8, 2, 1, 7, 2) \
+    SCTC_REC_T(X, 29, 25, 2, 6, 3, 1, 4, 2) SCTC_REC_T(X, 29, 25, 2, 8, 4, 1, 5, 2) SCTC_REC_T(X, 29, 25, 2, 8, 2, 1, 7, 2) \
+    SCTC_REC_T(X, 32, 31, 1, 8, 4, 1, 5, 2) SCTC_REC_T(X, 32, 31, 1, 6, 3, 1, 4, 2)                             \
+    SCTC_REC_T(X, 32, 31, 2, 8, 4, 1, 5, 2) SCTC_REC_T(X, 32, 31, 2, 6, 3, 1, 4, 2)
+
+static RecKernel rec_kernel(const RecCandidate& c)
 {
-    // two utterance tiles per wave (33..64 utterances) keep the round 1-4 order: there the loads of the second
-    // (last) batch are the only ones not under MFMAs, and the pipelined order measured SLOWER (13.1 -> 14.7 us per step
-    // at 64 utterances; 24.6 -> 21.6 at 128: profiles/r05_recurrence_large.md)
-    if constexpr (NTW >= 4) {
-        if (pipe) {
-            switch (nch_half) {
-                case 16: return brnn_recurrent_kernel<NTW, 16, true>;   // H = 512
-                case 32: return brnn_recurrent_kernel<NTW, 32, true>;   // H = 1024
-                case 57: return brnn_recurrent_kernel<NTW, 57, true>;   // H = 1824
-                case 64: return brnn_recurrent_kernel<NTW, 64, true>;   // H = 2048
-                default: break;
-            }
-        }
+#define SCTC_REC_MATCH(FAMILY, KERNEL, ...)                                                                     \
+    {                                                                                                           \
+        static constexpr int t[] = {__VA_ARGS__};                                                               \
+        constexpr int n = sizeof(t) / sizeof(t[0]);                                                             \
+        if (c.family == FAMILY && c.ntarg == n && std::equal(t, t + n, c.targ)) return KERNEL<__VA_ARGS__>;     \
     }
-    switch (nch_half) {
-        case 16: return brnn_recurrent_kernel<NTW, 16>;   // H = 512
-        case 32: return brnn_recurrent_kernel<NTW, 32>;   // H = 1024
-        case 57: return brnn_recurrent_kernel<NTW, 57>;   // H = 1824
-        case 64: return brnn_recurrent_kernel<NTW, 64>;   // H = 2048
-        default: return brnn_recurrent_kernel<NTW, 0>;
-    }
+    SCTC_REC_KERNELS(SCTC_REC_MATCH)
+#undef SCTC_REC_MATCH
+    return nullptr;     // a plan that names a kernel the library does not have: an error (launch_recurrent_one)
 }
 
 // ------------------------------------------------------------------ co-residency guards
@@ -1799,7 +1802,6 @@ void recurrent_set_shared_device_mode(int on) { g_shared_mode.store(on ? 1 : 0, 
 namespace {
 
 static constexpr double LEASE_WAIT_S = 30.0;
-static constexpr int Q1_MIN_B = 4;     // fewest utterances the single-chain flag kernel takes by default (below: the sentinel / VALU kernel; measured round 5, tools/rec_small_bench.py: 3 utterances 3.9 vs 4.6 us per step, 4: 4.9 vs 4.6, 5: 7.0 vs 4.5 at H = 1824)
 static double now_s()
 {
     struct timespec ts;
@@ -2024,7 +2026,7 @@ PersistentGate g_gate;
 // their __launch_bounds__ guarantee the registers for 1 or 2 blocks per CU; the runtime's
 // occupancy query under-reports kernels that use most of the 160 KiB -- it says 1 for the
 // two-chain kernel at 2 x 79 KiB, which does run two per CU -- so it is only the second opinion).
-static int prepare_kernel(RecKernel k, int threads, size_t smem, int max_per_cu, int dev, int* blocks_per_cu)
+static int prepare_kernel(RecKernel k, size_t smem, int max_per_cu, int dev, int* blocks_per_cu)
 {
     struct Info { size_t smem_set = 0; size_t occ_smem = (size_t)-1; int occ = 0; };
     static std::mutex mu;
@@ -2038,7 +2040,7 @@ static int prepare_kernel(RecKernel k, int threads, size_t smem, int max_per_cu,
     }
     if (in.occ_smem != smem) {
         int n = 0, lds = 0;
-        SCTC_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(k), threads, smem));
+        SCTC_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(k), REC_THREADS, smem));
         SCTC_HIP_TRY(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
         const int by_lds = smem ? (int)std::min<size_t>((size_t)max_per_cu, (size_t)lds / smem) : max_per_cu;
         in.occ = std::max(std::min(n, max_per_cu), by_lds);
@@ -2064,6 +2066,7 @@ struct LaunchCtx {
     int dev, cus;
     hipStream_t stream;
     int* path;      // out: REC_PATH_* of the last launch
+    int tcfg;       // SCTC_REC_TCFG
 };
 
 // launches a persistent grid if it can be co-resident (returns 1), else leaves it to the caller (0)
@@ -2076,11 +2079,11 @@ static int read_error_word(const RecArgs& a, hipStream_t stream, unsigned* e)
 }
 
 static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu, size_t sentinel_bytes,
-                             const RecArgs& a, const LaunchCtx& cx, bool* done, int threads = 256)
+                             const RecArgs& a, const LaunchCtx& cx, bool* done)
 {
     *done = false;
     int per_cu = 0;
-    SCTC_TRY(prepare_kernel(k, threads, smem, max_per_cu, cx.dev, &per_cu));
+    SCTC_TRY(prepare_kernel(k, smem, max_per_cu, cx.dev, &per_cu));
     if (per_cu < 1 || (int64_t)per_cu * cx.cus < grid) return SCTC_OK;
     const int need_cus = (grid + per_cu - 1) / per_cu;
     if (sentinel_bytes)   // sentinel-fill the exchange rows (both directions)
@@ -2099,7 +2102,7 @@ static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu,
         SCTC_HIP_TRY(hipStreamSynchronize(cx.stream));
         LeaseGuard lease(cx.dev);
         if (!lease.locked) return SCTC_OK;            // no lock file to be had: per-step fallback
-        hipLaunchKernelGGL(k, dim3(grid), dim3(threads), smem, cx.stream, a);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(REC_THREADS), smem, cx.stream, a);
         SCTC_HIP_TRY(hipGetLastError());
         // synchronous anyway: a time-out is reported by THIS launch, not found at the end of the step
         // behind later launches that ran on its garbage
@@ -2113,7 +2116,7 @@ static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu,
         return SCTC_OK;
     }
     SCTC_TRY(g_gate.admit_and_launch(cx.dev, cx.stream, need_cus, cx.cus, [&]() {
-        hipLaunchKernelGGL(k, dim3(grid), dim3(threads), smem, cx.stream, a);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(REC_THREADS), smem, cx.stream, a);
         return hipGetLastError();
     }));
     *done = true;
@@ -2123,220 +2126,31 @@ static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu,
 
 static int launch_recurrent_one(const RecArgs& a, const LaunchCtx& cx)
 {
-    const int nwg = a.Hp / 16;
-    const int ntiles = (a.B + 15) / 16;
-    hipStream_t stream = cx.stream;
-    bool done = false;
     // Step flags only: the error word (counters[2]) is STICKY across the launches of a step -- the
     // engine clears it once per step (recurrent_clear_error) and reads it once at the end, so a
     // forward-pass time-out is not wiped by the BPTT launch's memset, nor an earlier chunk's (more
     // than 128 utterances) by a later one's.
-    SCTC_HIP_TRY(hipMemsetAsync(a.counters + 32, 0, (REC_COUNTER_WORDS - 32) * sizeof(unsigned), stream));
-    if (a.variant == 3 || 2 * nwg > cx.cus) {
-        if (cx.path) *cx.path = REC_PATH_FALLBACK;
-        return launch_fallback(a, stream);
-    }
-    // measured at H=1824: 2.5 us per step for one utterance + ~1.2 us per further one (VALU FMAs),
-    // against 7.4 us for the flag/MFMA kernel: worth it up to 5 utterances
-    // 4..16 utterances are ONE 16-utterance chain: the flag kernel of the 17..32 case with a single chain per direction
-    // (one workgroup per CU instead of two).  Round 5 ("7.16 us at B = 16 is suspicious" -- it was): at
-    // H = 1824 it needs 4.66 / 4.57 / 4.80 / 4.97 us per step at 6 / 8 / 12 / 16 utterances where the sentinel / MFMA
-    // kernel below needs 4.92 / 5.00 / 6.09 / 7.16 (H = 2048: 5.45 against 7.31 at 16), with bit-identical costs and
-    // gradients (tools/rec_mid_bench.py): it is the default for fp32 operands; variant 42 keeps the sentinel kernel.
-    // At 4 and 5 utterances it also beats the sentinel / VALU kernel (whose step grows by 1 us per utterance and jumps at
-    // the fifth: 2.2 / 3.0 / 3.9 / 4.9 / 7.0 us for 1..5): variant 43 keeps that one up to 8, 44 forces this one from 1.
-    if ((!a.prec16 || a.B <= 5) && (a.B > Q1_MIN_B - 1 || a.variant == 44) && a.B <= 16 && a.variant != 1 && a.variant != 42 && a.variant != 43 &&
-        2 * nwg <= cx.cus) {
-        RecKernel qk = nullptr;
-        int ncq = 0, nreg = 0;
-        switch (nwg) {
-            case 32:  qk = brnn_recurrent_q_kernel<8, 0>;   ncq = 8;  nreg = 0;  break;  // H = 512
-            case 64:  qk = brnn_recurrent_q_kernel<16, 0>;  ncq = 16; nreg = 0;  break;  // H = 1024
-            case 114: qk = brnn_recurrent_q_kernel<29, 10>; ncq = 29; nreg = 10; break;  // H = 1824
-            case 128: qk = brnn_recurrent_q_kernel<32, 13>; ncq = 32; nreg = 13; break;  // H = 2048
-            default: break;
+    SCTC_HIP_TRY(hipMemsetAsync(a.counters + 32, 0, (REC_COUNTER_WORDS - 32) * sizeof(unsigned), cx.stream));
+    RecCandidate plan[REC_MAX_CANDIDATES];
+    const RecShape shape = {a.Hp, a.B, a.prec16, a.transpose, a.variant, cx.tcfg, cx.cus};
+    const int n = rec_plan(shape, plan);
+    for (int i = 0; i + 1 < n; ++i) {
+        const RecCandidate& c = plan[i];
+        const RecKernel k = rec_kernel(c);
+        if (!k) {
+            char name[96];
+            rec_candidate_name(c, name, sizeof(name));
+            return set_error(SCTC_ERR_ARG, "recurrent kernel: the plan names %s, which the library does not have", name);
         }
-        if (qk) {
-            RecArgs b = a;
-            b.linear_map = 1;   // linear block -> (chain, producer) map: chain = direction, tile 0 only (variant keeps its A/B meaning)
-            if (b.variant == 44) b.variant = 0;
-            const size_t smem = sizeof(float4) * ((size_t)4 * (ncq - nreg) * 64 + 3 * 64);
-            SCTC_TRY(launch_persistent(qk, 2 * nwg, smem, 2, 0, b, cx, &done));
-            if (done) return SCTC_OK;
-        }
-    }
-    if ((a.B <= 5 || (a.B <= 8 && a.variant == 43)) && a.variant != 1) {     // 43: the 8-utterance instantiation up to 8 (experiment)
-        RecKernel sk = nullptr;
-        const bool s4 = a.B <= 4;
-        switch (a.Hp / 32) {
-            case 16: sk = s4 ? brnn_recurrent_s_kernel<16, 4> : brnn_recurrent_s_kernel<16, 8>; break;   // H = 512
-            case 32: sk = s4 ? brnn_recurrent_s_kernel<32, 4> : brnn_recurrent_s_kernel<32, 8>; break;   // H = 1024
-            case 57: sk = s4 ? brnn_recurrent_s_kernel<57, 4> : brnn_recurrent_s_kernel<57, 8>; break;   // H = 1824
-            case 64: sk = s4 ? brnn_recurrent_s_kernel<64, 4> : brnn_recurrent_s_kernel<64, 8>; break;   // H = 2048
-            default: break;
-        }
-        if (sk) {
-            const size_t smem = sizeof(float) * 2 * (s4 ? 4 : 8) * a.Hp;
-            // <= 239 VGPRs and 58 KiB of LDS (1..4 utterances at H = 1824): TWO of these workgroups fit
-            // a CU, so the grids of two streams (one utterance per stream) can be co-resident -- the
-            // in-process gate counts this launch as half the device
-            SCTC_TRY(launch_persistent(sk, 2 * nwg, smem, 2, (size_t)2 * a.n_xrows * a.Hp * sizeof(float), a, cx, &done));
-            if (done) return SCTC_OK;
-        }
-    }
-    if (a.prec16 && a.B > 5 && a.B <= 16 && a.variant != 1) {
-        // "fp16 activations": 16-bit state exchange and weights (float16 forward, bfloat16 BPTT)
-        RecKernel hk = nullptr;
-        const bool bf = a.transpose != 0;
-        const int nch = a.Hp / 32;
-        switch ((nch + 3) / 4) {
-            case 4:  if (nch == 16) hk = bf ? brnn_recurrent_mh_kernel<4, true>  : brnn_recurrent_mh_kernel<4, false>;  break;  // H = 512
-            case 8:  if (nch == 32) hk = bf ? brnn_recurrent_mh_kernel<8, true>  : brnn_recurrent_mh_kernel<8, false>;  break;  // H = 1024
-            case 15: if (nch == 57) hk = bf ? brnn_recurrent_mh_kernel<15, true> : brnn_recurrent_mh_kernel<15, false>; break;  // H = 1824
-            case 16: if (nch == 64) hk = bf ? brnn_recurrent_mh_kernel<16, true> : brnn_recurrent_mh_kernel<16, false>; break;  // H = 2048
-            default: break;
-        }
-        const size_t smem = (((size_t)16 * (a.Hp + 8) * 2 + 15) / 16) * 16 + 3 * 64 * sizeof(float4);
-        if (hk && smem <= 160 * 1024) {
-            SCTC_TRY(launch_persistent(hk, 2 * nwg, smem, 1, (size_t)2 * a.n_xrows * a.Hp * 2, a, cx, &done));
-            if (done) return SCTC_OK;
-        }
-    }
-#ifdef SCTC_REC_EXPERIMENTS
-    if (a.B > 5 && a.B <= 16 && a.variant != 1) {
-        RecKernel mk = nullptr;
-        switch ((nwg + 3) / 4) {
-            case 8:  if (nwg == 32)  mk = brnn_recurrent_m_kernel<8>;  break;   // H = 512
-            case 16: if (nwg == 64)  mk = brnn_recurrent_m_kernel<16>; break;   // H = 1024
-            case 29: if (nwg == 114) mk = brnn_recurrent_m_kernel<29>; break;   // H = 1824
-            case 32: if (nwg == 128) mk = brnn_recurrent_m_kernel<32>; break;   // H = 2048
-            default: break;
-        }
-        const size_t smem = sizeof(float) * ((size_t)16 * (a.Hp + 4) + 3 * 256);
-        if (mk && smem <= 160 * 1024) {
-            SCTC_TRY(launch_persistent(mk, 2 * nwg, smem, 1, (size_t)2 * a.n_xrows * a.Hp * sizeof(float), a, cx, &done));
-            if (done) return SCTC_OK;
-        }
-    }
-#endif
-#ifdef SCTC_REC_EXPERIMENTS
-    // 17..32 utterances, both chains of a direction in one 8-wave workgroup (round 4); variant 4 keeps
-    // the two-workgroups-per-CU kernel of rounds 1-3
-    const int q8_variant = (a.variant >= 8 && a.variant < 40) ? a.variant : (a.variant == 0 ? REC_Q8_DEFAULT : 0);   // 40..: A/B switches of other kernels
-    if (ntiles == 2 && q8_variant >= 8) {
-        RecKernel k8 = nullptr;
-        switch (nwg) {
-            case 32:  k8 = brnn_recurrent_q8_kernel<8>;  break;   // H = 512
-            case 64:  k8 = brnn_recurrent_q8_kernel<16>; break;   // H = 1024
-            case 114: k8 = brnn_recurrent_q8_kernel<29>; break;   // H = 1824
-            case 128: k8 = brnn_recurrent_q8_kernel<32>; break;   // H = 2048
-            default: break;
-        }
-        const int grid = 8 * ((nwg + 3) / 4);
-        const size_t smem = sizeof(float4) * ((size_t)nwg * 64 + 6 * 64) + sizeof(unsigned) * Q8_SYNC_WORDS;
-        if (k8 && grid <= cx.cus && smem <= 160 * 1024) {
-            RecArgs b = a;
-            b.variant = q8_variant;
-            SCTC_TRY(launch_persistent(k8, grid, smem, 1, 0, b, cx, &done, 512));
-            if (done) return SCTC_OK;
-        }
-    }
-#endif
-    // 17..32 utterances, fp32 operands, H = 1824 / 2048 (round 7): the tiled kernel with 16 units x both utterance tiles of
-    // a direction per CU (UG = 1; 228 / 256 workgroups, one per CU), the tiles' steps alternating.  SCTC_REC_VARIANT=51
-    // keeps the two-chain kernel below (A/B; the same bits).  SCTC_REC_TCFG=1: six batches, ring of three; 3: the weight
-    // slab in LDS instead of the accumulation registers.
-    if (ntiles == 2 && !a.prec16 && (a.variant == 0 || a.variant == 46 || a.variant == 49) && 2 * nwg <= cx.cus) {
-        static const int tcfg = getenv("SCTC_REC_TCFG") ? atoi(getenv("SCTC_REC_TCFG")) : 0;
-        RecKernel tk = nullptr;
-        int nldsf = 0;
-        switch (nwg) {
-            case 114:   // H = 1824
-                tk = tcfg == 1 ? brnn_recurrent_t_kernel<29, 29, 1, 6, 3, 1, 4, 1> : tcfg == 3 ? brnn_recurrent_t_kernel<29, 0, 1, 8, 4, 1, 5, 1>
-                     : brnn_recurrent_t_kernel<29, 29, 1, 8, 4, 1, 5, 1>;
-                nldsf = tcfg == 3 ? 29 : 0;
-                break;
-            case 128:   // H = 2048
-                tk = tcfg == 1 ? brnn_recurrent_t_kernel<32, 32, 1, 6, 3, 1, 4, 1> : tcfg == 3 ? brnn_recurrent_t_kernel<32, 0, 1, 8, 4, 1, 5, 1>
-                     : brnn_recurrent_t_kernel<32, 32, 1, 8, 4, 1, 5, 1>;
-                nldsf = tcfg == 3 ? 32 : 0;
-                break;
-            default: break;
-        }
-        if (tk) {
-            size_t smem = sizeof(float4) * 64 * ((size_t)4 * nldsf + 2 * 3 * 1) + (16 * 8 + 8 * 32) * sizeof(unsigned);
-            // with the slab in registers the kernel would leave room for a second workgroup on a CU: claim more than half
-            // of the 160 KiB so that every workgroup has a CU of its own (the co-residency check counts CUs)
-            smem = std::max(smem, (size_t)81 * 1024);
-            SCTC_TRY(launch_persistent(tk, 2 * nwg, smem, 1, 0, a, cx, &done));
-            if (done) return SCTC_OK;     // otherwise: the two-chain kernel below
-        }
-    }
-    if (ntiles == 2 && a.variant != 1 && 4 * nwg <= 2 * cx.cus && (4 * nwg) % 8 == 0) {
-        // two chains per CU; NREG keeps the LDS share of the slab at <= 76 KiB per workgroup
-        RecKernel qk = nullptr;
-        int ncq = 0, nreg = 0;
-        switch (nwg) {
-            case 32:  qk = brnn_recurrent_q_kernel<8, 0>;   ncq = 8;  nreg = 0;  break;  // H = 512
-            case 64:  qk = brnn_recurrent_q_kernel<16, 0>;  ncq = 16; nreg = 0;  break;  // H = 1024
-            case 114: qk = brnn_recurrent_q_kernel<29, 10>; ncq = 29; nreg = 10; break;  // H = 1824
-            case 128: qk = brnn_recurrent_q_kernel<32, 13>; ncq = 32; nreg = 13; break;  // H = 2048
-            default: break;
-        }
-        if (qk) {
-            const size_t smem = sizeof(float4) * ((size_t)4 * (ncq - nreg) * 64 + 3 * 64);
-            SCTC_TRY(launch_persistent(qk, 4 * nwg, smem, 2, 0, a, cx, &done));
-            if (done) return SCTC_OK;     // otherwise: the one-workgroup-per-CU kernel below
-        }
-    }
-    // 33..128 utterances: 32 units x half the utterance tiles per CU, two alternating sub-chains (round 6);
-    // variants 1 / 40 / 47 keep the one-slab-per-CU kernel below
-    // (H = 512 / 1024: 64 / 128 workgroups, no faster than the one-slab-per-CU kernel on as many CUs -- 9.3 against 8.4 us per
-    // step at H = 1024, 64 utterances: there the tiled form runs only when asked for, SCTC_REC_VARIANT=50: tests)
-    if (ntiles > 2 && a.variant != 1 && a.variant != 40 && a.variant != 47 && 4 * (a.Hp / 32) <= cx.cus &&
-        (a.Hp >= 1824 || a.variant == 50)) {
-        RecKernel tk = nullptr;
-        const bool one = ntiles <= 4;       // one utterance tile per sub-chain
-        int nldsf = 0;
-        // <chunks per wave, weight fragments in registers, tiles per sub-chain, batches per phase, ring depth, publish batch,
-        // batch in front of which the next phase's flags are checked>; SCTC_REC_TCFG=1: the other of (eight batches, ring of
-        // four) / (six, three) (A/B of the schedule, tools/rec_tiled_sweep.sh: equal within the noise); 2: ring of two (one batch of lookahead: 128 utterances
-        // 19.5 instead of 17.2 us per step -- the ring's depth is what hides the exchange loads' latency)
-        static const int tcfg = getenv("SCTC_REC_TCFG") ? atoi(getenv("SCTC_REC_TCFG")) : 0;
-        switch (nwg) {
-            case 32:  tk = one ? brnn_recurrent_t_kernel<8, 0, 1, 4, 2, 0, 3>  : brnn_recurrent_t_kernel<8, 0, 2, 4, 2, 0, 3>;  nldsf = 16; break;  // H = 512
-            case 64:  tk = one ? brnn_recurrent_t_kernel<16, 0, 1, 4, 2, 1, 3> : brnn_recurrent_t_kernel<16, 0, 2, 4, 2, 1, 3>; nldsf = 32; break;  // H = 1024
-            case 114:   // H = 1824
-                nldsf = 33;
-                if (one) tk = tcfg == 1 ? brnn_recurrent_t_kernel<29, 25, 1, 6, 3, 1, 4> : tcfg == 2 ? brnn_recurrent_t_kernel<29, 25, 1, 8, 2, 1, 7>
-                              : brnn_recurrent_t_kernel<29, 25, 1, 8, 4, 1, 5>;
-                else tk = tcfg == 1 ? brnn_recurrent_t_kernel<29, 25, 2, 8, 4, 1, 5> : tcfg == 2 ? brnn_recurrent_t_kernel<29, 25, 2, 8, 2, 1, 7>
-                          : brnn_recurrent_t_kernel<29, 25, 2, 6, 3, 1, 4>;     // (8, 4: 128 ring registers, 28 of them parked in the other file)
-                break;
-            case 128:   // H = 2048
-                nldsf = 33;
-                if (one) tk = tcfg == 1 ? brnn_recurrent_t_kernel<32, 31, 1, 6, 3, 1, 4> : brnn_recurrent_t_kernel<32, 31, 1, 8, 4, 1, 5>;
-                else tk = tcfg == 1 ? brnn_recurrent_t_kernel<32, 31, 2, 6, 3, 1, 4> : brnn_recurrent_t_kernel<32, 31, 2, 8, 4, 1, 5>;
-                break;
-            default: break;
-        }
-        if (tk) {
-            const size_t smem = sizeof(float4) * 64 * ((size_t)4 * nldsf + 2 * 3 * (one ? 2 : 4)) + (16 * 8 + 8 * 32) * sizeof(unsigned);
-            SCTC_TRY(launch_persistent(tk, 4 * (a.Hp / 32), smem, 1, 0, a, cx, &done));
-            if (done) return SCTC_OK;
-        }
-    }
-    const int ntw = ntiles <= 2 ? 1 : (ntiles <= 4 ? 2 : 4);
-    const size_t smem = sizeof(float4) * ((size_t)nwg * 64 + 2 * ntw * 64);
-    if (smem <= 160 * 1024) {
-        const bool pipe = a.variant != 40;     // 40: exchange loads and MFMAs of a batch one after the other (rounds 1-4; A/B)
-        RecKernel kern = ntw == 1 ? pick_kernel<1>(nwg / 2, false)
-                         : (ntw == 2 ? pick_kernel<2>(nwg / 2, pipe) : pick_kernel<4>(nwg / 2, pipe));
-        SCTC_TRY(launch_persistent(kern, 2 * nwg, smem, 1, 0, a, cx, &done));
-        if (done) return SCTC_OK;
+        RecArgs b = a;
+        b.linear_map = c.linear_map;
+        b.variant = c.variant;
+        bool done = false;
+        SCTC_TRY(launch_persistent(k, c.grid, c.lds, c.per_cu, (size_t)2 * a.n_xrows * a.Hp * c.fill, b, cx, &done));
+        if (done) return SCTC_OK;       // otherwise the device cannot co-reside this grid: the next candidate
     }
     if (cx.path) *cx.path = REC_PATH_FALLBACK;
-    return launch_fallback(a, stream);
+    return launch_fallback(a, cx.stream);
 }
 
 int recurrent_clear_error(unsigned* counters, hipStream_t stream)
@@ -2352,6 +2166,8 @@ int launch_recurrent(const RecArgs& a_in, hipStream_t stream, int* path)
     char why[128];
     if (!recurrent_supported(a.Hp, a.B, why, sizeof(why)))
         return set_error(SCTC_ERR_ARG, "recurrent kernel: %s", why);
+    if (!rec_variant_known(a.variant))
+        return set_error(SCTC_ERR_ARG, "recurrent kernel: SCTC_REC_VARIANT=%d is not a variant (RecVariant, csrc/recurrent_plan.h)", a.variant);
     if (a.Tmax <= 0 || a.B <= 0) return SCTC_OK;
     if ((size_t)a.n_xrows * a.Hp * sizeof(float) >= ((size_t)1 << 31))
         return set_error(SCTC_ERR_ARG, "recurrent kernel: %d exchange rows x %d units exceed the "
@@ -2361,33 +2177,21 @@ int launch_recurrent(const RecArgs& a_in, hipStream_t stream, int* path)
     cx.path = path;
     cx.dev = 0;
     cx.cus = 0;
+    static const int tcfg = getenv("SCTC_REC_TCFG") ? atoi(getenv("SCTC_REC_TCFG")) : 0;
+    cx.tcfg = tcfg;
     SCTC_HIP_TRY(hipGetDevice(&cx.dev));
     SCTC_HIP_TRY(hipDeviceGetAttribute(&cx.cus, hipDeviceAttributeMultiprocessorCount, cx.dev));
     // utterances are independent: more than 128 run as consecutive launches of <= 128 (sorted by
     // length, so a later launch covers no more steps than its first utterance has frames)
-    constexpr int MAXB = 128;
     for (int b0 = 0; b0 < a_in.B;) {
-        int nb = std::min(MAXB, a_in.B - b0);
-        // How a minibatch is cut into launches (utterances are independent, sorted by length: a later launch covers only as
-        // many steps as ITS longest utterance has).  Round 6, with the units x utterances kernel (tools/rec_tiled_sweep.sh,
-        // H = 1824, us per time step, equal lengths): 33..64 utterances in ONE launch (40 / 48: 10.5 against 11.2 / 11.7 for
-        // 32 + the rest, round 5's cut); 65..96 as 64 + the rest (72 / 80: 15.0 against 18.7 in one launch of the two-tile
-        // form, which multiplies its empty tile slots; 96 = 64 + 32: 9.5 + 6.4); 97..128 in one launch (18.7).
-        // Variant 45: never cut.  Kernels without the tiled form (variants 1 / 40 / 47, other layer sizes) keep round 5's cuts.
-        const bool tiled = ((a.variant == 0 && (a.Hp == 1824 || a.Hp == 2048)) || (a.variant == 50 && (a.Hp == 512 || a.Hp == 1024 || a.Hp == 1824 || a.Hp == 2048))) &&
-                           !a.prec16 && 4 * (a.Hp / 32) <= cx.cus;
-        if (tiled) {
-            if (nb > 64 && nb <= 96) nb = 64;
-        } else {
-            if (nb > 32 && nb <= 48 && a.variant == 0 && !a.prec16) nb = 32;
-            else if (nb > 64 && nb <= 80 && a.variant == 0 && !a.prec16) nb = 64;
-        }
+        const RecShape rest = {a.Hp, a_in.B - b0, a.prec16, a.transpose, a.variant, cx.tcfg, cx.cus};
+        const int nb = rec_cut(rest);
         RecArgs c = a;
         c.b_off = a_in.b_off + b0;
         c.T_b = a_in.T_b + b0;
         c.B = nb;
         if (a_in.T_host) c.Tmax = std::min(a_in.Tmax, (int)a_in.T_host[b0]);
-        if (c.variant == 45) c.variant = 0;
+        if (c.variant == REC_V_NO_CUT) c.variant = REC_V_AUTO;
         SCTC_TRY(launch_recurrent_one(c, cx));
         b0 += nb;
     }

@@ -395,8 +395,8 @@ def _c(path, H, B, variant="0", mode="f32", NL=2, TL=1, Tmax=None, rec_path=(1, 
                            id="%s-H%d-B%d-v%s-%s" % (path, H, B, variant, mode))
 
 
-# path names follow launch_recurrent_one / launch_recurrent (csrc/recurrent.hip), which also cuts some minibatches into
-# two launches (noted per row).  mode: "f32" | "bf16x3" | "f16" (NNet(fp16=True)).
+# path names follow rec_plan / rec_cut (csrc/recurrent_plan.h; rec_cut cuts some minibatches into two launches, noted per
+# row): tests/test_recurrence_plan_cpu.py holds every row to its name.  mode: "f32" | "bf16x3" | "f16" (NNet(fp16=True)).
 GPU_CASES = (
     # 1..3 utterances: sentinel / VALU kernel, 4-utterance instantiation (the flag kernel takes over at 4)
     [_c("s4", H, B) for H in (512, 1824) for B in (1, 3)]

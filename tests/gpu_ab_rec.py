@@ -1,6 +1,6 @@
 """A/B of recurrent-kernel variants on the headline shapes (cfg-3, minibatch 32): the variants named
 on the command line (SCTC_REC_VARIANT values) must give bit-identical costs and gradients; prints
-step time and phase times of each.  usage: gpu_ab_rec.py [T=1000] [variants=0,4] [B=32]"""
+step time and phase times of each (the first one is the reference).  usage: gpu_ab_rec.py T VARIANTS [B=32], e.g. 1000 0,51"""
 import ctypes
 import os
 import sys
@@ -21,8 +21,10 @@ PHASES = ["fwd_gemm", "fwd_rec", "ctc", "bwd_gemm", "bwd_rec", "other"]
 
 
 def main():
-    T = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
-    variants = [v for v in (sys.argv[2] if len(sys.argv) > 2 else "0,4").split(",")]
+    if len(sys.argv) < 3:
+        sys.exit(__doc__)
+    T = int(sys.argv[1])
+    variants = sys.argv[2].split(",")
     B = int(sys.argv[3]) if len(sys.argv) > 3 else 32
     D, A, H, NL, TL, U = 483, 33, 1824, 5, 3, max(1, T // 10)
     rs = np.random.RandomState(1)

@@ -477,8 +477,7 @@ def test_recurrent_mid_batch_kernel(mods, monkeypatch, H, B):
     """6..16 utterances (4..16 since the crossover measurement): since round 5 the flag kernel with ONE chain per
     direction (brnn_recurrent_q_kernel on half its grid).  Ragged minibatch against the one-workgroup-per-CU flag
     kernel (SCTC_REC_VARIANT=1) and, at H=512, the oracle.  (The sentinel-exchange MFMA kernel it replaced,
-    brnn_recurrent_m_kernel / variant 42, agreed bit for bit in round 5 and is compiled only with
-    -DSCTC_REC_EXPERIMENTS since round 6.)"""
+    brnn_recurrent_m_kernel, agreed bit for bit in round 5; it left the tree after commit 1cbab82.)"""
     variant = "0"
     _, brnnet, obrnn, _ = mods
     rs = np.random.RandomState(31 * H + B)

@@ -16,8 +16,10 @@ the tiled kernel in its three forms (units x both tiles per CU; one / two tiles 
 request, the small layers, the one-slab-per-CU kernel with 1 / 2 / 4 tiles per wave, its generic instantiation at
 layer sizes without a specialised kernel, the per-step fallback, and the cuts of launch_recurrent (32 + 8, 64 + 16,
 never, 128 + 22).  recurrentPath() only tells persistent (1) from per-step (3): which kernel a persistent launch
-runs follows from (H, B, operand type, SCTC_REC_VARIANT) by the dispatch as read, not from an observable of the
-engine.  SCTC_REC_TCFG is read once per process and is left out.
+runs follows from (H, B, operand type, SCTC_REC_VARIANT) by rec_plan / rec_cut (csrc/recurrent_plan.h), not from an
+observable of the engine; tests/test_recurrence_plan_cpu.py asserts for every row of the matrix that the plan's first
+candidate is the family the row's id names, and for the cut rows the launch sizes.  SCTC_REC_TCFG is read once per
+process and is left out.
 
 What this file does not cover: the arithmetic error of the forward recurrence on non-integer data (the oracle tests of
 test_gpu_brnn / test_gpu_fullsize / gpu_fuzz keep that), and the backward pass of the fp16-operand configuration.

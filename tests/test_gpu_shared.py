@@ -80,6 +80,22 @@ def test_per_step_fallback_vs_persistent_and_oracle(mods, monkeypatch, H, B):
     assert netf.recurrentPath()[0] == 3 and netp.recurrentPath()[0] == 1
 
 
+def test_unknown_recurrence_variant_is_an_error(mods, monkeypatch):
+    """SCTC_REC_VARIANT=42 named a kernel that is gone: no silent run of the default kernel under that name, the step
+    raises and says which value; a fresh net with the variable back at 0 runs"""
+    _, brnnet, obrnn, _ = mods
+    D, A, H, NL, TL, Ts = 24, 12, 64, 3, 2, [4, 3]
+    params, datas, labs = _problem(obrnn, 42, D, A, H, NL, TL, Ts)
+    monkeypatch.setenv("SCTC_REC_VARIANT", "42")
+    net = make_net(brnnet, (D, A, H, NL, TL, max(Ts)), params, maxUtts=len(Ts))
+    with pytest.raises(ValueError, match=r"SCTC_REC_VARIANT=42\b"):       # SCTC_ERR_ARG
+        net.costAndGradBatch(datas, labs)
+    monkeypatch.setenv("SCTC_REC_VARIANT", "0")
+    net0 = make_net(brnnet, (D, A, H, NL, TL, max(Ts)), params, maxUtts=len(Ts))
+    costs, _, skips = net0.costAndGradBatch(datas, labs)
+    assert net0.recurrentPath() == (1, 1, 0) and np.isfinite(costs[~skips]).all()
+
+
 def test_layer_wider_than_the_device_runs_per_step(mods):
     """H = 2304 needs 2 x 144 = 288 co-resident workgroups on a 256-CU part: rounds 1-2 rejected
     such layers, now they run on the per-step recurrence (the reference has no such limit:
