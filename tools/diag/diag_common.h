@@ -13,8 +13,10 @@
 
 namespace sctc {
 
-char* diag_err_buf();
-int set_error(int code, const char* fmt, ...);
+// hidden: libsctc_diag.so links against libsctc_hip.so (gemm_entry.hip), which has a sctc::set_error of its
+// own -- neither library may bind to the other's
+__attribute__((visibility("hidden"))) char* diag_err_buf();
+__attribute__((visibility("hidden"))) int set_error(int code, const char* fmt, ...);
 
 #define SCTC_HIP_TRY(expr)                                                                   \
     do {                                                                                     \

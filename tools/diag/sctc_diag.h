@@ -3,6 +3,8 @@
  * the kernels of libsctc_hip.so.  NOT part of the drop-in boundary (include/sctc.h): nothing in
  * stanford-ctc_amd/ loads this library; tests/gpu_diag.py, bench.py's "sustained peak" note and
  * __graft_entry__.smoke() do.  These entry points allocate (and free) their own scratch memory.
+ * The library links against libsctc_hip.so for one purpose: sctc_diag_gemm below, the tests' door to the
+ * product's own GEMM launcher.
  */
 #ifndef SCTC_DIAG_H_
 #define SCTC_DIAG_H_
@@ -41,6 +43,47 @@ int sctc_diag_stream_destroy(void* stream);
 /* n_wgs workgroups of 256 threads, each holding its CU for hold_us: out_host[4 * i + {0,1,2,3}] =
  * XCC id, shader engine, shader array, CU id of workgroup i (synchronous) */
 int sctc_diag_where(int32_t* out_host, int32_t n_wgs, int32_t hold_us, void* stream);
+
+/* ---- test-only door to the product library's GEMM launcher (gemm_entry.hip; tests/test_gpu_gemm_options.py).
+ * A plain-C mirror of sctc::GemmArgs (stanford-ctc_amd/csrc/gemm_f32.h), field for field and in its order;
+ * sctc_diag_gemm copies it into a GemmArgs and calls sctc::launch_gemm_f32 OF libsctc_hip.so (this
+ * library links against it: no second compilation of the kernels).  Errors: -1 / -2 with the message in the
+ * PRODUCT library's sctc_last_error(). */
+typedef struct sctc_diag_gemm_args {
+    const void* A;          /* fp32, or 16-bit elements with in16 */
+    const void* B;
+    float* C;
+    int64_t lda, ldb, ldc;
+    int32_t M, N, K;
+    int32_t a_kcontig, b_kcontig;
+    const int32_t* idx_a;
+    const int32_t* idx_b;
+    const float* bias;
+    const float* mask;
+    int64_t ldmask;
+    const float* addend;
+    int64_t ldadd;
+    float add_scale;
+    int32_t relu;
+    int32_t accumulate;
+    float* colsum_a;
+    float* splitk_ws;       /* splits * M * (N + 1) floats when splits > 1 */
+    int32_t splits;
+    int32_t prec;           /* 0 fp32, 1 float16, 2 bfloat16, 3 bf16x3 */
+    int32_t in16;
+    uint16_t* C16a;
+    uint16_t* C16b;
+    int64_t ldc16;
+    int32_t skip_c32;
+    const uint16_t* mask16;
+    int64_t ldmask16;
+    const float* A2;
+    float* a_sum;
+} sctc_diag_gemm_args;
+int sctc_diag_gemm(const sctc_diag_gemm_args* args, void* stream);
+/* sctc::gemm_plan_splits: the split-K count the product picks for this shape (through *splits) and the
+ * workspace floats it needs (0 when *splits == 1) */
+int64_t sctc_diag_gemm_plan_splits(int32_t M, int32_t N, int32_t K, int32_t prec, int32_t in16, int32_t* splits);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,31 @@
-"""ctypes loader of tools/diag/libsctc_diag.so (hardware probes; not the product library)."""
+"""ctypes loader of tools/diag/libsctc_diag.so (hardware probes and the test-only GEMM entry; not the product
+library)."""
 import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsctc_diag.so")
 _lib = None
+
+
+class GemmArgs(ctypes.Structure):
+    """sctc_diag_gemm_args of sctc_diag.h: sctc::GemmArgs (csrc/gemm_f32.h) field for field"""
+    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p),
+                ("lda", ctypes.c_int64), ("ldb", ctypes.c_int64), ("ldc", ctypes.c_int64),
+                ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("a_kcontig", ctypes.c_int32), ("b_kcontig", ctypes.c_int32),
+                ("idx_a", ctypes.c_void_p), ("idx_b", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p),
+                ("mask", ctypes.c_void_p), ("ldmask", ctypes.c_int64),
+                ("addend", ctypes.c_void_p), ("ldadd", ctypes.c_int64),
+                ("add_scale", ctypes.c_float), ("relu", ctypes.c_int32), ("accumulate", ctypes.c_int32),
+                ("colsum_a", ctypes.c_void_p),
+                ("splitk_ws", ctypes.c_void_p), ("splits", ctypes.c_int32),
+                ("prec", ctypes.c_int32), ("in16", ctypes.c_int32),
+                ("C16a", ctypes.c_void_p), ("C16b", ctypes.c_void_p), ("ldc16", ctypes.c_int64),
+                ("skip_c32", ctypes.c_int32),
+                ("mask16", ctypes.c_void_p), ("ldmask16", ctypes.c_int64),
+                ("A2", ctypes.c_void_p), ("a_sum", ctypes.c_void_p)]
 
 
 def lib():
@@ -27,5 +48,8 @@ def lib():
         L.sctc_diag_stream_destroy.argtypes = [ctypes.c_void_p]
         L.sctc_diag_where.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_void_p]
+        L.sctc_diag_gemm.argtypes = [ctypes.POINTER(GemmArgs), ctypes.c_void_p]
+        L.sctc_diag_gemm_plan_splits.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)]
+        L.sctc_diag_gemm_plan_splits.restype = ctypes.c_int64
         _lib = L
     return _lib
