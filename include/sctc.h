@@ -287,6 +287,66 @@ int sctc_ctc_nnbeam_decode_batch(const sctc_nnbeam_config* cfg, const void* prob
                                  int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
                                  size_t workspace_bytes, void* stream);
 
+/* ---- decoding with a recurrent character LM: the `rnn` model type of clm_decoder2.pyx -----
+ * Added without an ABI version bump (still 6): sctc_rnnlm_create / sctc_rnnlm_destroy / sctc_rnnlm_bytes /
+ * sctc_rnnlm_step, sctc_ctc_rnnbeam_workspace_bytes, sctc_ctc_rnnbeam_decode_batch. */
+
+/* A recurrent character LM on the device (stanford-ctc_amd/nn_lm.py, RNNCharLM, holds the model file):
+ *   h(empty prefix) = relu(bh + Wx[:, <s>]),  h(P) = relu(bh + Wx[:, id of P's last symbol] + Wh h(P without it)),
+ *   row(P) = log10 softmax(Wo h(P) + bo).  All float32, the log-softmax in float64.
+ *   vocab 3..256;  hidden a multiple of 32 in 32..2048 (pad with zero units: relu(0) = 0)
+ *   Wx [hidden][vocab], Wh [hidden][hidden], Wo [vocab][hidden] row-major, bh [hidden], bo [vocab], on the host
+ *   bos_id   the id of <s>, fed into the zero state for the empty prefix
+ * The one allocating call: the parameters are repacked and uploaded, and the scratch of sctc_rnnlm_step
+ * is part of the handle, which lives until sctc_rnnlm_destroy. */
+typedef struct sctc_rnnlm* sctc_rnnlm_t;
+int sctc_rnnlm_create(int32_t vocab, int32_t hidden, const float* wx_host, const float* wh_host,
+                      const float* bh_host, const float* wo_host, const float* bo_host, int32_t bos_id,
+                      sctc_rnnlm_t* out);
+int sctc_rnnlm_destroy(sctc_rnnlm_t lm);
+/* bytes of device memory the LM holds (0 for NULL) */
+size_t sctc_rnnlm_bytes(sctc_rnnlm_t lm);
+
+/* One recurrent step of n independent pairs: state_out_dev[i * hidden ..] = relu(bh + Wx[:, ids_dev[i]] +
+ * Wh state_in_dev[i * hidden ..]) and, unless rows_dev is NULL, rows_dev[i * vocab + v] = log10 P(v | that
+ * state).  state_in_dev NULL: every input state is zero.  An id outside 0..vocab-1 is clamped into it.  A
+ * state and a row are functions of the pair alone, to the bit: not of n, of the pair's position, or of who
+ * asks (the search evaluates the same routine).  Allocates nothing; calls on one handle share its scratch
+ * and must be ordered on one stream.  The LM must live on the current device. */
+int sctc_rnnlm_step(sctc_rnnlm_t lm, const int32_t* ids_dev, const float* state_in_dev, int64_t n,
+                    float* state_out_dev, float* rows_dev, void* stream);
+
+/* The prefix beam search of sctc_ctc_beam_decode_batch with the LM term alpha * log10 P_RNN(c | <s> prefix).
+ * The fields of sctc_nnbeam_config with the recurrent LM's handle. */
+typedef struct sctc_rnnbeam_config {
+    int32_t B;                 /* utterances */
+    int32_t A;                 /* symbols incl. blank, 2..256 */
+    int32_t dtype;             /* SCTC_F32 | SCTC_F64: type of probs */
+    int32_t beam;              /* 1..256 */
+    int32_t nbest;             /* hypotheses returned per utterance, 1..beam */
+    int32_t reserved;          /* 0 */
+    int64_t ld;                /* row stride of probs in elements (>= A) */
+    const int32_t* T_b;        /* host [B] */
+    const int64_t* frame_off;  /* host [B] */
+    double alpha;              /* LM weight */
+    double beta;               /* length bonus */
+    sctc_rnnlm_t lm;           /* required */
+    const int32_t* sym_word;   /* host [A]: LM id (0..vocab-1) of symbols 1..A-1 */
+} sctc_rnnbeam_config;
+
+/* bytes of device workspace (0: rejected, sctc_last_error()): per utterance what
+ * sctc_ctc_beam_workspace_bytes reports with an LM, 8 * beam * hidden bytes of states (two beams) and one
+ * tile of the LM (256 * hidden + 128 * (vocab padded to 32) + 512 bytes) */
+size_t sctc_ctc_rnnbeam_workspace_bytes(const sctc_rnnbeam_config* cfg);
+
+/* Outputs as sctc_ctc_beam_decode_batch writes them.  Allocates nothing.  The LM must live on the current
+ * device.  Diagnostic: with SCTC_RNNBEAM_STATE_COPIES=2..4 in the environment the kernel copies the states of
+ * the carried entries that many times per frame instead of once; no result changes, and the time added is a
+ * lower estimate of what the copy costs (the repeats find their lines in L2; tools/decode_rnn_bench.py). */
+int sctc_ctc_rnnbeam_decode_batch(const sctc_rnnbeam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                                  int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                                  size_t workspace_bytes, void* stream);
+
 /* ---- scoring: ctc_fast/editDistance.py, ctc_fast/swbd-utils/editDist.pyx -----
  * Added without an ABI version bump (still 6): sctc_edit_distance_workspace_bytes,
  * sctc_edit_distance_batch. */

@@ -71,6 +71,10 @@ class NNBeamConfig(ctypes.Structure):
                 ("sym_word", c_i32p)]
 
 
+class RNNBeamConfig(ctypes.Structure):
+    _fields_ = list(NNBeamConfig._fields_)
+
+
 class EditConfig(ctypes.Structure):
     _fields_ = [("P", ctypes.c_int32), ("flags", ctypes.c_int32), ("a_len", c_i32p), ("a_off", c_i64p),
                 ("b_len", c_i32p), ("b_off", c_i64p)]
@@ -129,6 +133,14 @@ PROTOTYPES = {
     "sctc_ctc_nnbeam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(NNBeamConfig)]),
     "sctc_ctc_nnbeam_decode_batch": (ctypes.c_int, [ctypes.POINTER(NNBeamConfig), vp, vp, vp, vp, vp,
                                                     ctypes.c_size_t, vp]),
+    "sctc_rnnlm_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32,
+                                         ctypes.POINTER(vp)]),
+    "sctc_rnnlm_destroy": (ctypes.c_int, [vp]),
+    "sctc_rnnlm_bytes": (ctypes.c_size_t, [vp]),
+    "sctc_rnnlm_step": (ctypes.c_int, [vp, vp, vp, ctypes.c_int64, vp, vp, vp]),
+    "sctc_ctc_rnnbeam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(RNNBeamConfig)]),
+    "sctc_ctc_rnnbeam_decode_batch": (ctypes.c_int, [ctypes.POINTER(RNNBeamConfig), vp, vp, vp, vp, vp,
+                                                     ctypes.c_size_t, vp]),
     "sctc_edit_distance_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(EditConfig), ctypes.POINTER(ctypes.c_size_t)]),
     "sctc_edit_distance_batch": (ctypes.c_int, [ctypes.POINTER(EditConfig), vp, vp, vp, vp, vp, vp, ctypes.c_size_t,
                                                 vp]),

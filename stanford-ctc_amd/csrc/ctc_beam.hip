@@ -25,12 +25,20 @@
 // beam entry carries the window of the last K LM ids of <null>.. <s> + P, copied from its parent and
 // shifted on extension, and step 4 evaluates the rows of the new entries in tiles of 32 through
 // nnlm_tile (nnlm_dev.h), the routine sctc_nnlm_rows runs.
+//
+// A fourth instantiation (RNN) takes the rows from a recurrent neural LM (the `rnn` model type of
+// clm_decoder2.pyx): every beam entry carries the LM's hidden state of its prefix,
+// copied from its parent when carried over; step 4 makes one recurrent step per new entry, from the
+// parent's state and the new symbol, in tiles of 32 through rnnlm_tile (rnnlm_dev.h), the routine
+// sctc_rnnlm_step runs.
 #include <math.h>
+#include <stdlib.h>
 
 #include <vector>
 
 #include "common.h"
 #include "nnlm_dev.h"
+#include "rnnlm_dev.h"
 
 struct sctc_lm {
     uint64_t* key = nullptr;   // device [cap]; prob / backoff follow in the same allocation
@@ -110,6 +118,12 @@ struct NNArgs {
     NNLMDev m;
 };
 struct NoNNArgs {
+};
+// the recurrent LM search only
+struct RNNArgs {
+    RNNLMDev m;
+    int32_t state_copies;   // 1; SCTC_RNNBEAM_STATE_COPIES = 2..4 repeats the copy of the carried states, which
+                            // changes no result: the time it adds is what the copy costs (tools/decode_rnn_bench.py)
 };
 constexpr int WIN = NN_MAX_CONTEXT;   // bytes of a beam entry's context window (one LM id per byte)
 
@@ -286,9 +300,11 @@ __device__ inline double load_prob(const BeamArgs& p, int64_t row, int c)
     return p.f64 ? ((const double*)p.probs)[row * p.ld + c] : (double)((const float*)p.probs)[row * p.ld + c];
 }
 
-template <bool LEX, bool NN, typename NNA>
+// NN: a neural LM supplies the rows -- the window model, or with RNN the recurrent one
+template <bool LEX, bool NN, bool RNN, typename NNA>
 __device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
 {
+    static_assert(NN || !RNN, "the recurrent LM is a neural LM");
     __shared__ Beam bm[2];
     __shared__ LexState<LEX> lx[2];
     __shared__ HTab tab[2];
@@ -320,7 +336,19 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
     float* nn_act = nullptr;
     float* nn_rows = nullptr;
     int32_t* nn_ids = nullptr;
-    if constexpr (NN) {
+    // RNN: the hidden states of both beams, [2][K][H], then the scratch of one LM tile
+    float* st[2] = {nullptr, nullptr};
+    int32_t* nn_slot = nullptr;
+    if constexpr (RNN) {
+        const int H = nn.m.H;
+        st[0] = (float*)w;
+        st[1] = st[0] + (size_t)K * H;
+        w += al256((size_t)2 * K * H * sizeof(float));
+        nn_act = (float*)w;
+        nn_rows = (float*)(w + nn_act_bytes(H));
+        nn_slot = (int32_t*)(w + nn_act_bytes(H) + nn_row_bytes(nn.m.Vp));
+        w += rnn_tile_bytes(H, nn.m.Vp);
+    } else if constexpr (NN) {
         win[0] = (uint8_t*)w;
         win[1] = win[0] + (size_t)K * WIN;
         w += al256((size_t)2 * K * WIN);
@@ -355,7 +383,17 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
     }
     __syncthreads();
     if (tid == 0) htab_insert(tab[0], H_EMPTY_PREFIX, 0);
-    if constexpr (NN) {
+    if constexpr (RNN) {
+        // the empty prefix: <s> into the zero state
+        if (tid == 0) {
+            nn_slot[0] = nn.m.bos;
+            nn_slot[NN_TILE] = 0;
+            nn_slot[2 * NN_TILE] = 0;
+        }
+        __syncthreads();
+        rnnlm_tile(nn.m, nn_slot, 1, nullptr, st[0], nn_act, nn_rows);
+        for (int c = tid; c < A; c += NT) rows[0][c] = c == 0 ? 0.0f : nn_rows[p.sym_word[c]];
+    } else if constexpr (NN) {
         // the empty prefix: <null> .. <null> <s>
         const int CK = nn.m.K;
         for (int s = tid; s < CK; s += NT) {
@@ -546,7 +584,7 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
                     NX.wd[r] = X.wd[j];
                     NX.bg[r] = X.bg[j];
                 }
-                if constexpr (NN) {
+                if constexpr (NN && !RNN) {
                     const uint4* src = (const uint4*)(win[cb] + (size_t)j * WIN);
                     uint4* dst = (uint4*)(win[cb ^ 1] + (size_t)r * WIN);
                     dst[0] = src[0];
@@ -570,7 +608,7 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
                     NX.wd[r] = wd;
                     NX.bg[r] = wd >= 0 ? lex_bg(p, pw, wd) : 0.0f;
                 }
-                if constexpr (NN) {
+                if constexpr (NN && !RNN) {
                     // the parent's window, one slot older, and the new symbol's LM id
                     const uint8_t* src = win[cb] + (size_t)j * WIN;
                     uint8_t* dst = win[cb ^ 1] + (size_t)r * WIN;
@@ -594,22 +632,53 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
                 const int src = NB.prev[r];
                 if (src >= 0) rows[rb ^ 1][it] = rows[rb][src * A + (it - r * A)];
             }
+            if constexpr (RNN) {
+                // a carried entry keeps its state: a copy into the new beam's buffer
+                const int Hq = nn.m.H >> 2;
+                const float4* so = (const float4*)st[cb];
+                float4* sn = (float4*)st[cb ^ 1];
+                for (int pass = 0; pass < nn.state_copies; ++pass)
+                    for (int it = tid; it < nsel * Hq; it += NT) {
+                        const int r = it / Hq;
+                        const int src = NB.prev[r];
+                        if (src >= 0) sn[it] = so[(size_t)src * Hq + (it - r * Hq)];
+                    }
+            }
             // the new entries in rank order, 32 to a tile (sel_idx is free until the next select)
             const int fresh = tid < nsel && NB.prev[tid] < 0;
             int n_new;
             const int pos = block_excl_scan(fresh, scan_scratch, &n_new);
             if (fresh) sel_idx[pos] = tid;
             __syncthreads();
-            const int CK = nn.m.K, Vp = nn.m.Vp;
-            const uint8_t* wn = win[cb ^ 1];
+            const int Vp = nn.m.Vp;
+            int CK = 0;
+            const uint8_t* wn = nullptr;
+            if constexpr (!RNN) {
+                CK = nn.m.K;
+                wn = win[cb ^ 1];
+            }
             for (int t0 = 0; t0 < n_new; t0 += NN_TILE) {
                 const int cnt = min(NN_TILE, n_new - t0);
-                for (int i = tid; i < cnt * CK; i += NT) {
-                    const int e = i / CK, s = i - e * CK;
-                    nn_ids[i] = wn[(size_t)sel_idx[t0 + e] * WIN + s];
+                if constexpr (RNN) {
+                    // the parent j and the symbol c as step 3 recorded them: the parent's state is in
+                    // the old beam's buffer, the entry's goes to the new one
+                    if (tid < cnt) {
+                        const int r = sel_idx[t0 + tid];
+                        const int ev = rec[(int64_t)t * K + r];
+                        nn_slot[tid] = p.sym_word[ev & 0xFFFF];
+                        nn_slot[NN_TILE + tid] = ev >> 16;
+                        nn_slot[2 * NN_TILE + tid] = r;
+                    }
+                    __syncthreads();
+                    rnnlm_tile(nn.m, nn_slot, cnt, st[cb], st[cb ^ 1], nn_act, nn_rows);
+                } else {
+                    for (int i = tid; i < cnt * CK; i += NT) {
+                        const int e = i / CK, s = i - e * CK;
+                        nn_ids[i] = wn[(size_t)sel_idx[t0 + e] * WIN + s];
+                    }
+                    __syncthreads();
+                    nnlm_tile(nn.m, nn_ids, cnt, nn_act, nn_rows);
                 }
-                __syncthreads();
-                nnlm_tile(nn.m, nn_ids, cnt, nn_act, nn_rows);
                 for (int i = tid; i < cnt * A; i += NT) {
                     const int e = i / A, c = i - e * A;
                     rows[rb ^ 1][sel_idx[t0 + e] * A + c] = c == 0 ? 0.0f : nn_rows[(size_t)e * Vp + p.sym_word[c]];
@@ -657,11 +726,13 @@ __device__ __forceinline__ void beam_search(const BeamArgs& p, const NNA& nn)
     }
 }
 
-__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p) { beam_search<false, false>(p, NoNNArgs{}); }
+__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs p) { beam_search<false, false, false>(p, NoNNArgs{}); }
 
-__global__ __launch_bounds__(NT) void ctc_lexbeam_kernel(BeamArgs p) { beam_search<true, false>(p, NoNNArgs{}); }
+__global__ __launch_bounds__(NT) void ctc_lexbeam_kernel(BeamArgs p) { beam_search<true, false, false>(p, NoNNArgs{}); }
 
-__global__ __launch_bounds__(NT) void ctc_nnbeam_kernel(BeamArgs p, NNArgs nn) { beam_search<false, true>(p, nn); }
+__global__ __launch_bounds__(NT) void ctc_nnbeam_kernel(BeamArgs p, NNArgs nn) { beam_search<false, true, false>(p, nn); }
+
+__global__ __launch_bounds__(NT) void ctc_rnnbeam_kernel(BeamArgs p, RNNArgs nn) { beam_search<false, true, true>(p, nn); }
 
 struct BeamPlan {
     std::vector<UttDesc> utt;
@@ -757,6 +828,33 @@ int plan_nnbeam(const sctc_nnbeam_config* cfg, BeamPlan& pl)
     c.alpha = cfg->alpha;
     c.beta = cfg->beta;
     return plan_beam(&c, pl, al256((size_t)2 * cfg->beam * WIN) + nn_tile_bytes(m.hmax, m.Vp, m.K));
+}
+
+// the recurrent LM search plans like the character search with an LM, plus the states of both beams
+// and its LM tile
+int plan_rnnbeam(const sctc_rnnbeam_config* cfg, BeamPlan& pl)
+{
+    SCTC_CHECK_ARG(cfg, "rnnbeam: null config");
+    SCTC_CHECK_ARG(cfg->lm, "rnnbeam: null LM");
+    SCTC_CHECK_ARG(cfg->sym_word, "rnnbeam: null symbol -> LM id map");
+    SCTC_CHECK_ARG(cfg->A >= 2 && cfg->A <= AMAX, "rnnbeam: alphabet size %d outside 2..%d", cfg->A, AMAX);
+    SCTC_CHECK_ARG(cfg->beam >= 1 && cfg->beam <= KMAX, "rnnbeam: beam width %d outside 1..%d", cfg->beam, KMAX);
+    const RNNLMDev& m = cfg->lm->dev;
+    for (int c = 1; c < cfg->A; ++c)
+        SCTC_CHECK_ARG(cfg->sym_word[c] >= 0 && cfg->sym_word[c] < m.V,
+                       "rnnbeam: symbol %d maps to LM id %d outside 0..%d", c, cfg->sym_word[c], m.V - 1);
+    sctc_beam_config c{};
+    c.B = cfg->B;
+    c.A = cfg->A;
+    c.dtype = cfg->dtype;
+    c.beam = cfg->beam;
+    c.nbest = cfg->nbest;
+    c.ld = cfg->ld;
+    c.T_b = cfg->T_b;
+    c.frame_off = cfg->frame_off;
+    c.alpha = cfg->alpha;
+    c.beta = cfg->beta;
+    return plan_beam(&c, pl, al256((size_t)2 * cfg->beam * m.H * sizeof(float)) + rnn_tile_bytes(m.H, m.Vp));
 }
 
 }  // namespace
@@ -1065,6 +1163,69 @@ int sctc_ctc_nnbeam_decode_batch(const sctc_nnbeam_config* cfg, const void* prob
     NNArgs nn{};
     nn.m = cfg->lm->dev;
     hipLaunchKernelGGL(ctc_nnbeam_kernel, dim3(cfg->B), dim3(NT), 0, s, a, nn);
+    SCTC_HIP_TRY(hipGetLastError());
+    return SCTC_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+size_t sctc_ctc_rnnbeam_workspace_bytes(const sctc_rnnbeam_config* cfg)
+{
+    BeamPlan pl;
+    if (plan_rnnbeam(cfg, pl) != SCTC_OK) return 0;
+    return pl.total;
+}
+
+int sctc_ctc_rnnbeam_decode_batch(const sctc_rnnbeam_config* cfg, const void* probs_dev, int32_t* ids_dev,
+                                  int32_t* lengths_dev, double* scores_dev, void* workspace_dev,
+                                  size_t workspace_bytes, void* stream)
+{
+    BeamPlan pl;
+    SCTC_TRY(plan_rnnbeam(cfg, pl));
+    SCTC_CHECK_ARG(probs_dev && lengths_dev && scores_dev && workspace_dev, "rnnbeam: null device pointer");
+    int64_t total_T = 0;
+    for (int b = 0; b < cfg->B; ++b) total_T += cfg->T_b[b];
+    SCTC_CHECK_ARG(ids_dev || total_T == 0, "rnnbeam: null ids");
+    if (workspace_bytes < pl.total)
+        return set_error(SCTC_ERR_WORKSPACE, "rnnbeam: workspace %zu bytes < %zu needed", workspace_bytes, pl.total);
+    int dev = 0;
+    SCTC_HIP_TRY(hipGetDevice(&dev));
+    SCTC_CHECK_ARG(dev == cfg->lm->device, "rnnbeam: the LM lives on device %d, the current device is %d",
+                   cfg->lm->device, dev);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<char> head(pl.head, 0);
+    memcpy(head.data(), pl.utt.data(), cfg->B * sizeof(UttDesc));
+    const size_t sym_off = align256(cfg->B * sizeof(UttDesc));
+    memcpy(head.data() + sym_off, cfg->sym_word, cfg->A * sizeof(int32_t));
+    ((int32_t*)(head.data() + sym_off))[0] = 0;        // the blank has no LM id; never read
+    SCTC_HIP_TRY(hipMemcpyAsync(workspace_dev, head.data(), pl.head, hipMemcpyHostToDevice, s));
+    SCTC_HIP_TRY(hipStreamSynchronize(s));
+
+    BeamArgs a{};
+    a.probs = probs_dev;
+    a.ld = cfg->ld;
+    a.f64 = cfg->dtype == SCTC_F64;
+    a.A = cfg->A;
+    a.K = cfg->beam;
+    a.nbest = cfg->nbest;
+    a.alpha = cfg->alpha;
+    a.beta = cfg->beta;
+    a.utt = (const UttDesc*)workspace_dev;
+    a.sym_word = (const int32_t*)((char*)workspace_dev + sym_off);
+    a.ws = (char*)workspace_dev;
+    a.ids = ids_dev;
+    a.lens = lengths_dev;
+    a.scores = scores_dev;
+    RNNArgs nn{};
+    nn.m = cfg->lm->dev;
+    nn.state_copies = 1;
+    if (const char* e = getenv("SCTC_RNNBEAM_STATE_COPIES")) {
+        const int v = atoi(e);
+        if (v >= 1 && v <= 4) nn.state_copies = v;
+    }
+    hipLaunchKernelGGL(ctc_rnnbeam_kernel, dim3(cfg->B), dim3(NT), 0, s, a, nn);
     SCTC_HIP_TRY(hipGetLastError());
     return SCTC_OK;
 }

@@ -57,11 +57,22 @@ __host__ __device__ inline size_t nn_tile_bytes(int hmax, int Vp, int K)
 
 typedef float nn_f32x16 __attribute__((ext_vector_type(16)));
 
+// where a recurrent layer (REC, rnnlm_dev.h) leaves the new states: slot e < cnt to st + row[e] * Nout
+struct NNStateOut {
+    float* st;
+    const int32_t* row;
+    int cnt;
+};
+
 // one layer l >= 1 for the tile: TN unit tiles of 32 per wave and pass, all reading one activation
-// operand.  LAST: the output layer, stored as plain rows z[slot][Vp] without the relu.
-template <int TN, bool LAST>
+// operand.  LAST: the output layer, stored as plain rows z[slot][Vp] without the relu.  REC: the
+// recurrent layer of rnnlm_dev.h -- the accumulator starts from the pre-activation of its own slot,
+// which `out` holds in the quad layout (every lane reads exactly the quads it stores later, so the
+// result replaces it in place), and the result is also stored as the state of the slot's entry.
+template <int TN, bool LAST, bool REC = false>
 __device__ __forceinline__ void nn_layer(const float* __restrict__ W, const float* __restrict__ bias,
-                                         const float* __restrict__ in, float* __restrict__ out, int Hin, int Nout)
+                                         const float* __restrict__ in, float* __restrict__ out, int Hin, int Nout,
+                                         NNStateOut so = NNStateOut{})
 {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -75,7 +86,9 @@ __device__ __forceinline__ void nn_layer(const float* __restrict__ W, const floa
             const int tile = min(t0 + i, nt - 1);
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
-                const float4 bv = reinterpret_cast<const float4*>(bias)[tile * 8 + rq * 2 + g];
+                float4 bv;
+                if constexpr (REC) bv = reinterpret_cast<const float4*>(out)[(size_t)(tile * 8 + rq * 2 + g) * NN_TILE + e];
+                else bv = reinterpret_cast<const float4*>(bias)[tile * 8 + rq * 2 + g];
                 acc[i][4 * rq + 0] = bv.x;
                 acc[i][4 * rq + 1] = bv.y;
                 acc[i][4 * rq + 2] = bv.z;
@@ -125,8 +138,40 @@ __device__ __forceinline__ void nn_layer(const float* __restrict__ W, const floa
                     v.z = fmaxf(v.z, 0.0f);
                     v.w = fmaxf(v.w, 0.0f);
                     reinterpret_cast<float4*>(out)[(size_t)(tile * 8 + rq * 2 + g) * NN_TILE + e] = v;
+                    if constexpr (REC) {
+                        if (e < so.cnt)
+                            *reinterpret_cast<float4*>(so.st + (size_t)so.row[e] * Nout + tile * 32 + rq * 8 + g * 4) = v;
+                    }
                 }
             }
+        }
+    }
+}
+
+// rows[slot * Vp + v], v < V, of `cnt` slots: the outputs z on entry, log10 softmax(z) on return, in
+// float64, one wave per slot; V <= 256 = 4 values per lane
+__device__ __forceinline__ void nn_log10_softmax(float* rows, int cnt, int V, int Vp)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int e = wv; e < cnt; e += 4) {
+        double z[4], mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = lane + 64 * i;
+            z[i] = v < V ? (double)rows[(size_t)e * Vp + v] : -INFINITY;
+            mx = fmax(mx, z[i]);
+        }
+        for (int d = 32; d >= 1; d >>= 1) mx = fmax(mx, __shfl_xor(mx, d, 64));
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (lane + 64 * i < V) s += exp(z[i] - mx);
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+        const double lse = mx + log(s);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = lane + 64 * i;
+            if (v < V) rows[(size_t)e * Vp + v] = (float)((z[i] - lse) * 0.43429448190325182765);
         }
     }
 }
@@ -184,29 +229,7 @@ __device__ __forceinline__ void nnlm_tile(const NNLMDev& m, const int32_t* ids, 
         __syncthreads();
     }
 
-    // ---- log10 softmax in float64, one wave per context; V <= 256 = 4 values per lane ----
-    const int Vp = m.Vp;
-    for (int e = wv; e < cnt; e += 4) {
-        double z[4], mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int v = lane + 64 * i;
-            z[i] = v < V ? (double)rows[(size_t)e * Vp + v] : -INFINITY;
-            mx = fmax(mx, z[i]);
-        }
-        for (int d = 32; d >= 1; d >>= 1) mx = fmax(mx, __shfl_xor(mx, d, 64));
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (lane + 64 * i < V) s += exp(z[i] - mx);
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-        const double lse = mx + log(s);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int v = lane + 64 * i;
-            if (v < V) rows[(size_t)e * Vp + v] = (float)((z[i] - lse) * 0.43429448190325182765);
-        }
-    }
+    nn_log10_softmax(rows, cnt, V, m.Vp);
     __syncthreads();
 }
 

@@ -12,8 +12,8 @@ anything else raises ``ValueError`` like the memoryview does.  The float64 host
 signature runs the float64 device kernels.  Additional entry points (not in the
 reference) take batches and device tensors: :func:`ctc_loss_batch`; and the prefix beam
 search decoder of ``ctc_fast/new_decoder/decoder.pyx`` batched over utterances:
-:func:`decode_beam_batch` with an optional character LM (an n-gram :class:`DecodeLM` or a
-neural :class:`DecodeNNLM`); and scoring: :func:`edit_distance_batch` (the table and
+:func:`decode_beam_batch` with an optional character LM (an n-gram :class:`DecodeLM`, a
+neural :class:`DecodeNNLM` or a recurrent :class:`DecodeRNNLM`); and scoring: :func:`edit_distance_batch` (the table and
 trace-back of ``ctc_fast/editDistance.py`` and ``swbd-utils/editDist.pyx`` for many pairs in
 one launch), :func:`nbest_oracle`, and the forced alignment :func:`align_batch` with
 :func:`score_sentences` (the ``align`` and ``refScore`` of ``decoder_utils.decode``).
@@ -291,6 +291,124 @@ class DecodeNNLM(object):
             pass
 
 
+class DecodeRNNLM(object):
+    """A recurrent character LM on the device for :func:`decode_beam_batch`: an
+    :class:`nn_lm.RNNCharLM` (or the path of its ``.npz``) uploaded once, plus the LM id of every CTC
+    symbol -- ``symbols`` as for :class:`DecodeNNLM`.  Every symbol 1..A-1 must have an id (ValueError)."""
+
+    def __init__(self, rnnlm, symbols, A=None):
+        import nn_lm
+        if not isinstance(rnnlm, nn_lm.RNNCharLM):
+            rnnlm = nn_lm.RNNCharLM.load(rnnlm)
+        self.rnnlm = rnnlm
+        self.handle = None
+        if isinstance(symbols, dict):
+            A = int(A) if A is not None else max(symbols) + 1
+            self.sym_words = rnnlm.symbol_words(symbols, A)
+        else:
+            self.sym_words = np.ascontiguousarray(symbols, dtype=np.int32)
+            if A is not None:
+                self.sym_words = self.sym_words[:int(A)]
+            bad = [c for c in range(1, self.sym_words.shape[0]) if not 0 <= self.sym_words[c] < rnnlm.V]
+            if bad:
+                raise ValueError("DecodeRNNLM: symbol %d maps to LM id %d outside the vocabulary"
+                                 % (bad[0], self.sym_words[bad[0]]))
+        self.Hp, Wx, Wh, bh, Wo = rnnlm.padded()
+        _sctc.require_gpu()
+        h = ctypes.c_void_p()
+        rc = _sctc.lib().sctc_rnnlm_create(rnnlm.V, self.Hp, Wx.ctypes.data, Wh.ctypes.data, bh.ctypes.data,
+                                           Wo.ctypes.data, rnnlm.bo.ctypes.data, rnnlm.bos, ctypes.byref(h))
+        _sctc.check(rc, "DecodeRNNLM")
+        self.handle = h
+        self.device_bytes = int(_sctc.lib().sctc_rnnlm_bytes(h))
+
+    def step(self, ids, state_in=None, rows=True):
+        """One recurrent step on device tensors: ids int32 [n], state_in float32 [n, Hp] or None (zero
+        states) -> (state_out [n, Hp], rows [n, V] or None)"""
+        torch = _sctc.require_gpu()
+        if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 1
+                and ids.is_contiguous()):
+            raise ValueError("DecodeRNNLM.step: ids must be a contiguous int32 [n] tensor on the device")
+        n = int(ids.shape[0])
+        if state_in is not None and not (isinstance(state_in, torch.Tensor) and state_in.device == ids.device
+                                         and state_in.dtype == torch.float32 and state_in.is_contiguous()
+                                         and tuple(state_in.shape) == (n, self.Hp)):
+            raise ValueError("DecodeRNNLM.step: state_in must be a contiguous float32 [%d, %d] tensor on the device of "
+                             "ids, or None" % (n, self.Hp))
+        out = torch.empty((n, self.Hp), dtype=torch.float32, device=ids.device)
+        r = torch.empty((n, self.rnnlm.V), dtype=torch.float32, device=ids.device) if rows else None
+        rc = _sctc.lib().sctc_rnnlm_step(self.handle, ids.data_ptr(), state_in.data_ptr() if state_in is not None else None,
+                                         n, out.data_ptr(), r.data_ptr() if rows else None,
+                                         _sctc.current_stream_ptr())
+        _sctc.check(rc, "DecodeRNNLM.step")
+        return out, r
+
+    def _evaluate(self, prefixes, cache=None):
+        """[(state [Hp] on the device, LM row [V] on the host)] of prefixes (sequences of CTC symbol ids):
+        every distinct prefix, and every prefix of it, is evaluated once, one step call per prefix
+        depth.  ``cache``: a dict of the caller's that keeps what was evaluated from call to call."""
+        torch = _sctc.require_gpu()
+        want = [tuple(int(s) for s in P) for P in prefixes]
+        known = cache if cache is not None else {}
+        levels = []
+        for P in want:
+            if any(not 1 <= s < self.sym_words.shape[0] for s in P):
+                raise ValueError("DecodeRNNLM: a prefix holds a symbol outside 1..%d" % (self.sym_words.shape[0] - 1))
+            for d in range(len(P), -1, -1):
+                if P[:d] in known:
+                    break
+                while len(levels) <= d:
+                    levels.append({})
+                levels[d].setdefault(P[:d], None)
+        for d, level in enumerate(levels):
+            todo = list(level)
+            if not todo:
+                continue
+            if d == 0:
+                ids, state_in = [self.rnnlm.bos], None
+            else:
+                ids = [self.sym_words[P[-1]] for P in todo]
+                state_in = torch.stack([known[P[:-1]][0] for P in todo])
+            out, rows = self.step(torch.from_numpy(np.asarray(ids, dtype=np.int32)).cuda(), state_in)
+            rows = rows.cpu().numpy()
+            for i, P in enumerate(todo):
+                known[P] = (out[i], rows[i])
+        return [known[P] for P in want]
+
+    def states(self, prefixes, cache=None):
+        """float32 [n, H]: the hidden state of every prefix (a sequence of CTC symbol ids)"""
+        torch = _sctc.require_gpu()
+        got = self._evaluate(prefixes, cache)
+        if not got:
+            return np.zeros((0, self.rnnlm.H), dtype=np.float32)
+        return np.ascontiguousarray(torch.stack([s for s, _ in got]).cpu().numpy()[:, :self.rnnlm.H])
+
+    def lm_rows(self, prefixes, cache=None):
+        """float32 [n, V]: log10 P(. | <s> prefix) by LM id"""
+        got = self._evaluate(prefixes, cache)
+        return np.stack([r for _, r in got]) if got else np.zeros((0, self.rnnlm.V), dtype=np.float32)
+
+    def rows(self, prefixes, cache=None):
+        """float32 [n, A] as the search sees them: column 0 is 0, column c is log10 P(symbol c |
+        prefix) for every prefix (a sequence of CTC symbol ids of any length).  Distinct prefixes are
+        evaluated once, one step call per prefix depth; with ``cache`` (a dict of the caller's) the
+        states of evaluated prefixes are kept from call to call."""
+        out = self.lm_rows(prefixes, cache)[:, self.sym_words]
+        out[:, 0] = 0.0
+        return np.ascontiguousarray(out)
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            _sctc.lib().sctc_rnnlm_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _decode_inputs(logprobs, lengths, what):
     """(host arrays or None, device tensor or None, A, T_b, numpy dtype, sctc dtype) of a decode call"""
     import torch
@@ -362,13 +480,14 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
 
     logprobs: list of (A, T_b) float32/float64 natural-log probability arrays (symbol 0 the
     blank), or a torch device tensor [sum T][A] with ``lengths`` giving T_b.  lm: a
-    :class:`DecodeLM`, a :class:`DecodeNNLM` or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
+    :class:`DecodeLM`, a :class:`DecodeNNLM`, a :class:`DecodeRNNLM` (§4.10) or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
     of int32 symbol-id arrays and float64[B]; with nbest > 1 a list of lists and [B, nbest]
     (entries beyond the beam: empty, -inf)."""
     arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, "decode_beam_batch")
     B = len(T_b)
-    if lm is not None and not isinstance(lm, (DecodeLM, DecodeNNLM)):
-        raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM or None")
+    if lm is not None and not isinstance(lm, (DecodeLM, DecodeNNLM, DecodeRNNLM)):
+        raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM, a "
+                         "ctc_fast.DecodeRNNLM or None")
     if lm is not None and lm.sym_words.shape[0] < A:
         raise ValueError("decode_beam_batch: the LM maps %d symbols, the input has %d"
                          % (lm.sym_words.shape[0], A))
@@ -382,6 +501,11 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
         cfg = _sctc.NNBeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
                                  float(alpha), float(beta), lm.handle, _sctc.i32(sw))
         return _decode_launch(cfg, L.sctc_ctc_nnbeam_workspace_bytes, L.sctc_ctc_nnbeam_decode_batch, arrs, src, A,
+                              T_b, dt, nbest, "decode_beam_batch")
+    if isinstance(lm, DecodeRNNLM):
+        cfg = _sctc.RNNBeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
+                                  float(alpha), float(beta), lm.handle, _sctc.i32(sw))
+        return _decode_launch(cfg, L.sctc_ctc_rnnbeam_workspace_bytes, L.sctc_ctc_rnnbeam_decode_batch, arrs, src, A,
                               T_b, dt, nbest, "decode_beam_batch")
     return _decode_launch(cfg, L.sctc_ctc_beam_workspace_bytes, L.sctc_ctc_beam_decode_batch, arrs, src, A, T_b,
                           dt, nbest, "decode_beam_batch")
@@ -640,10 +764,10 @@ def align_batch(logprobs, seqs, lengths=None, blank=0, total=False):
 
 
 def lm_sentence_scores(seqs, lm):
-    """float64 [B]: sum_i log10 P_LM(l_i | <s>, l_<i) of every label row under ``lm`` (a :class:`DecodeLM`
-    or a :class:`DecodeNNLM`), the float32 values that the beam search adds, summed in float64; no
-    end-of-sentence term.  An n-gram LM is scored on the host (``ArpaLM.score_ids``), the neural LM by
-    one ``DecodeNNLM.rows`` call over all prefixes."""
+    """float64 [B]: sum_i log10 P_LM(l_i | <s>, l_<i) of every label row under ``lm`` (a :class:`DecodeLM`,
+    a :class:`DecodeNNLM` or a :class:`DecodeRNNLM`), the float32 values that the beam search adds, summed in float64; no
+    end-of-sentence term.  An n-gram LM is scored on the host (``ArpaLM.score_ids``), a neural LM by
+    one ``rows`` call over all prefixes."""
     out = np.zeros(len(seqs), dtype=np.float64)
     if isinstance(lm, DecodeLM):
         for b, s in enumerate(seqs):
@@ -653,8 +777,8 @@ def lm_sentence_scores(seqs, lm):
                 out[b] += float(lm.arpa.score_ids(ctx, w))
                 ctx.append(w)
         return out
-    if not isinstance(lm, DecodeNNLM):
-        raise ValueError("lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM or None")
+    if not isinstance(lm, (DecodeNNLM, DecodeRNNLM)):
+        raise ValueError("lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM, a ctc_fast.DecodeRNNLM or None")
     prefixes = [tuple(int(c) for c in s[:i]) for s in seqs for i in range(len(s))]
     if prefixes:
         rows = lm.rows(prefixes)
@@ -677,8 +801,9 @@ def score_sentences(logprobs, seqs, lengths=None, lm=None, alpha=1.0, beta=0.0):
     _, _, _, total, status = align_batch(logprobs, rows, lengths=lengths, total=True)
     score = np.full(len(rows), -np.inf, dtype=np.float64)
     ok = status == 0
-    if lm is not None and not isinstance(lm, (DecodeLM, DecodeNNLM)):
-        raise ValueError("score_sentences: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM or None")
+    if lm is not None and not isinstance(lm, (DecodeLM, DecodeNNLM, DecodeRNNLM)):
+        raise ValueError("score_sentences: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM, a "
+                         "ctc_fast.DecodeRNNLM or None")
     good = [r if o else r[:0] for r, o in zip(rows, ok)]
     lmv = lm_sentence_scores(good, lm) if lm is not None else np.zeros(len(rows))
     for b in np.nonzero(ok)[0]:

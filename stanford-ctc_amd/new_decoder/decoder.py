@@ -10,7 +10,7 @@ the same classes and calls, decoding on the MI355X through libsctc_hip.so.
 ``probs`` is a float64 (A, T) Fortran-ordered array of natural-log probabilities, as the
 ``double[::1,:]`` memoryview accepts; anything else raises like the memoryview does.  The
 LM is an ARPA file read by arpa_lm.py (kenlm is not needed), or -- a path ending in ``.npz`` -- the
-neural character LM of nn_lm.py.  ``decode_batch`` (not in
+neural character LM of nn_lm.py (with ``kind = "rnn"`` the recurrent one, §4.10).  ``decode_batch`` (not in
 the reference) decodes a list of utterances in one launch.
 """
 import numpy as np
@@ -94,7 +94,7 @@ class BeamLMDecoder(DecoderBase):
     def load_lm(self, lmfile):
         if str(lmfile).endswith(".npz"):
             import nn_lm
-            self.lm = nn_lm.NNCharLM.load(lmfile)
+            self.lm = nn_lm.load(lmfile)        # the window model or, kind = "rnn", the recurrent one
         else:
             self.lm = arpa_lm.ArpaLM(lmfile)
         self._dev = {}
@@ -106,7 +106,9 @@ class BeamLMDecoder(DecoderBase):
         if self.int_char_map is None:
             raise ValueError("BeamLMDecoder: load_chars first")
         if A not in self._dev:
-            cls = ctc_fast.DecodeLM if isinstance(self.lm, arpa_lm.ArpaLM) else ctc_fast.DecodeNNLM
+            import nn_lm
+            cls = ctc_fast.DecodeLM if isinstance(self.lm, arpa_lm.ArpaLM) else \
+                ctc_fast.DecodeRNNLM if isinstance(self.lm, nn_lm.RNNCharLM) else ctc_fast.DecodeNNLM
             self._dev[A] = cls(self.lm, self.int_char_map, A)
         return self._dev[A]
 

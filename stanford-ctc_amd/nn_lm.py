@@ -17,6 +17,9 @@ there).  ``clm_decoder2`` multiplies natural logs: its alpha is this alpha divid
 
 The model file is an ``.npz`` with ``tokens`` (V strings), ``context`` (K) and ``W0..WL`` /
 ``b0..bL`` (float32, W_l row-major [outputs][inputs]).  tools/train_char_nnlm.py writes one.
+
+:class:`RNNCharLM` is the same search's ``rnn`` model type; its file says
+``kind = "rnn"``, and :func:`load` returns the class a file asks for.
 """
 import numpy as np
 
@@ -121,3 +124,76 @@ class NNCharLM(object):
             bs.append(bp)
             widths.append(rows)
         return np.asarray(widths, dtype=np.int32), ws, bs
+
+
+class RNNCharLM(object):
+    """The recurrent character LM of DESIGN.md §4.10, the ``rnn`` model type of ``clm_decoder2.pyx``
+    (its lines 43-80): the hidden state is a function of the prefix, cached per prefix by the search.
+
+        h(())  = relu(bh + Wx[:, <s>] + Wh 0)                 the empty prefix feeds <s> into no state
+        h(P)   = relu(bh + Wx[:, id(P[-1])] + Wh h(P[:-1]))   a prefix feeds its last symbol only
+        row(P) = log10 softmax(Wo h(P) + bo)
+
+    ReLU and log10 as for :class:`NNCharLM`.  The model file is an ``.npz`` with ``kind = "rnn"``,
+    ``tokens`` (V strings, the rule of NNCharLM; ``<null>`` is never fed) and ``Wx [H][V]``,
+    ``Wh [H][H]``, ``bh [H]``, ``Wo [V][H]``, ``bo [V]`` (float32).  tools/train_char_nnlm.py --rnn
+    writes one."""
+
+    def __init__(self, tokens, Wx, Wh, bh, Wo, bo):
+        self.tokens = [str(t) for t in tokens]
+        self.V = len(self.tokens)
+        self.Wx, self.Wh, self.Wo = (np.ascontiguousarray(w, dtype=np.float32) for w in (Wx, Wh, Wo))
+        self.bh, self.bo = (np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in (bh, bo))
+        if not 3 <= self.V <= MAX_VOCAB:
+            raise ValueError("RNNCharLM: vocabulary of %d tokens outside 3..%d" % (self.V, MAX_VOCAB))
+        if len(set(self.tokens)) != self.V:
+            raise ValueError("RNNCharLM: a token is listed twice")
+        for t in SPECIALS:
+            if t not in self.tokens:
+                raise ValueError("RNNCharLM: the vocabulary has no %s" % t)
+        if self.Wx.ndim != 2 or not 1 <= self.Wx.shape[0] <= MAX_WIDTH:
+            raise ValueError("RNNCharLM: Wx is %s; [H][V] with H in 1..%d is expected" % (self.Wx.shape, MAX_WIDTH))
+        self.H = H = self.Wx.shape[0]
+        for name, a, shape in (("Wx", self.Wx, (H, self.V)), ("Wh", self.Wh, (H, H)), ("bh", self.bh, (H,)),
+                               ("Wo", self.Wo, (self.V, H)), ("bo", self.bo, (self.V,))):
+            if a.shape != shape:
+                raise ValueError("RNNCharLM: %s is %s, %s is expected" % (name, a.shape, shape))
+        self.vocab = {t: i for i, t in enumerate(self.tokens)}
+        self.null, self.bos, self.eos = (self.vocab[t] for t in SPECIALS)
+
+    symbol_words = NNCharLM.symbol_words
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            if "kind" not in z.files or str(z["kind"]) != "rnn":
+                raise ValueError("RNNCharLM: %s is not a recurrent model file (kind = \"rnn\")" % path)
+            return cls([str(t) for t in z["tokens"]], z["Wx"], z["Wh"], z["bh"], z["Wo"], z["bo"])
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, kind=np.array("rnn"), tokens=np.array(self.tokens), Wx=self.Wx, Wh=self.Wh, bh=self.bh,
+                     Wo=self.Wo, bo=self.bo)
+
+    def padded(self):
+        """(Hp, Wx, Wh, bh, Wo) with H zero-padded to a multiple of 32.  The padding is exact: a padded
+        unit is relu(0) = 0 and its outgoing weights are 0."""
+        H, Hp = self.H, (self.H + 31) // 32 * 32
+        Wx = np.zeros((Hp, self.V), dtype=np.float32)
+        Wh = np.zeros((Hp, Hp), dtype=np.float32)
+        bh = np.zeros(Hp, dtype=np.float32)
+        Wo = np.zeros((self.V, Hp), dtype=np.float32)
+        Wx[:H], Wh[:H, :H], bh[:H], Wo[:, :H] = self.Wx, self.Wh, self.bh, self.Wo
+        return Hp, Wx, Wh, bh, Wo
+
+
+def load(path):
+    """the model of an ``.npz`` file: an :class:`RNNCharLM` when its ``kind`` says "rnn", else (no
+    ``kind``) the feed-forward :class:`NNCharLM`"""
+    with np.load(path, allow_pickle=False) as z:
+        kind = str(z["kind"]) if "kind" in z.files else None
+    if kind is None:
+        return NNCharLM.load(path)
+    if kind == "rnn":
+        return RNNCharLM.load(path)
+    raise ValueError("nn_lm.load: %s has the unknown kind %r" % (path, kind))
