@@ -1,0 +1,14 @@
+// Limits and table conventions that the prefix beam search (beam_search.h, beam_policies.h) and the
+// handles of its table LMs (beam_lm.hip) both hold to.
+#pragma once
+#include <stdint.h>
+
+namespace sctc {
+namespace beam {
+
+constexpr int AMAX = 256;               // alphabet limit
+constexpr int KMAX = 256;               // beam limit
+constexpr uint64_t BG_EMPTY = ~0ull;    // an empty slot of the lexicon's bigram table
+
+}  // namespace beam
+}  // namespace sctc

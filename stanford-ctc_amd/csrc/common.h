@@ -34,7 +34,8 @@ int set_error(int code, const char* fmt, ...);
     } while (0)
 
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the one rounding of workspace slices, on both sides of a launch
+__host__ __device__ static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Pinned host staging for small per-call descriptor uploads.  A hipMemcpyAsync from PAGEABLE memory beyond a few
 // tens of KB makes the runtime pin and unpin the source around the copy while the stream (and the GPU behind it)

@@ -20,8 +20,7 @@
 // multiple of 32 with zero rows) or tile slot (activations), so that every operand load and every
 // activation store is one float4 per lane, consecutive across the lanes.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "common.h"
 
 namespace sctc {
 
@@ -44,10 +43,9 @@ struct NNLMDev {
 };
 
 // scratch of one tile: two activation buffers, the rows, the context ids
-__host__ __device__ inline size_t nn_al256(size_t v) { return (v + 255) & ~(size_t)255; }
-__host__ __device__ inline size_t nn_act_bytes(int hmax) { return nn_al256((size_t)2 * NN_TILE * hmax * sizeof(float)); }
-__host__ __device__ inline size_t nn_row_bytes(int Vp) { return nn_al256((size_t)NN_TILE * Vp * sizeof(float)); }
-__host__ __device__ inline size_t nn_ids_bytes(int K) { return nn_al256((size_t)NN_TILE * K * sizeof(int32_t)); }
+__host__ __device__ inline size_t nn_act_bytes(int hmax) { return align256((size_t)2 * NN_TILE * hmax * sizeof(float)); }
+__host__ __device__ inline size_t nn_row_bytes(int Vp) { return align256((size_t)NN_TILE * Vp * sizeof(float)); }
+__host__ __device__ inline size_t nn_ids_bytes(int K) { return align256((size_t)NN_TILE * K * sizeof(int32_t)); }
 __host__ __device__ inline size_t nn_tile_bytes(int hmax, int Vp, int K)
 {
     return nn_act_bytes(hmax) + nn_row_bytes(Vp) + nn_ids_bytes(K);

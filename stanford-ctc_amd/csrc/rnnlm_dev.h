@@ -40,7 +40,7 @@ struct RNNLMDev {
 constexpr int RNN_SLOT_INTS = 3 * NN_TILE;
 __host__ __device__ inline size_t rnn_tile_bytes(int H, int Vp)
 {
-    return nn_act_bytes(H) + nn_row_bytes(Vp) + nn_al256(RNN_SLOT_INTS * sizeof(int32_t));
+    return nn_act_bytes(H) + nn_row_bytes(Vp) + align256(RNN_SLOT_INTS * sizeof(int32_t));
 }
 
 #ifdef __HIPCC__

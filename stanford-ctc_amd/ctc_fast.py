@@ -179,11 +179,31 @@ def collapse_best_path(best_path, blank=0):
     return hyp, align
 
 
-class DecodeLM(object):
+class _DeviceHandle(object):
+    """``handle`` of a device object of the library, destroyed once by the function ``_destroy`` names"""
+
+    _destroy = None
+    handle = None
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            getattr(_sctc.lib(), self._destroy)(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecodeLM(_DeviceHandle):
     """A character n-gram LM on the device for :func:`decode_beam_batch`: an
     :class:`arpa_lm.ArpaLM` (or the path of an ARPA file) packed and uploaded once, plus
     the LM word of every CTC symbol -- ``symbols`` is the decoder's ``int_char_map``
     ({symbol id: token}, chars.txt) or an int32 array of word ids per symbol."""
+
+    _destroy = "sctc_lm_destroy"
 
     def __init__(self, arpa, symbols, A=None):
         import arpa_lm
@@ -204,23 +224,14 @@ class DecodeLM(object):
         _sctc.check(rc, "DecodeLM")
         self.handle = h
 
-    def close(self):
-        if self.handle is not None and self.handle.value:
-            _sctc.lib().sctc_lm_destroy(self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DecodeNNLM(object):
+class DecodeNNLM(_DeviceHandle):
     """A neural character LM on the device for :func:`decode_beam_batch`: an
     :class:`nn_lm.NNCharLM` (or the path of its ``.npz``) uploaded once, plus the LM id of every
     CTC symbol -- ``symbols`` is the decoder's ``int_char_map`` ({symbol id: token}, chars.txt) or
     an int32 array of LM ids per symbol.  Every symbol 1..A-1 must have an id (ValueError)."""
+
+    _destroy = "sctc_nnlm_destroy"
 
     def __init__(self, nnlm, symbols, A=None):
         import nn_lm
@@ -279,22 +290,13 @@ class DecodeNNLM(object):
         out[:, 0] = 0.0
         return np.ascontiguousarray(out)
 
-    def close(self):
-        if self.handle is not None and self.handle.value:
-            _sctc.lib().sctc_nnlm_destroy(self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DecodeRNNLM(object):
+class DecodeRNNLM(_DeviceHandle):
     """A recurrent character LM on the device for :func:`decode_beam_batch`: an
     :class:`nn_lm.RNNCharLM` (or the path of its ``.npz``) uploaded once, plus the LM id of every CTC
     symbol -- ``symbols`` as for :class:`DecodeNNLM`.  Every symbol 1..A-1 must have an id (ValueError)."""
+
+    _destroy = "sctc_rnnlm_destroy"
 
     def __init__(self, rnnlm, symbols, A=None):
         import nn_lm
@@ -397,17 +399,6 @@ class DecodeRNNLM(object):
         out[:, 0] = 0.0
         return np.ascontiguousarray(out)
 
-    def close(self):
-        if self.handle is not None and self.handle.value:
-            _sctc.lib().sctc_rnnlm_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _decode_inputs(logprobs, lengths, what):
     """(host arrays or None, device tensor or None, A, T_b, numpy dtype, sctc dtype) of a decode call"""
@@ -485,33 +476,32 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
     (entries beyond the beam: empty, -inf)."""
     arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, "decode_beam_batch")
     B = len(T_b)
-    if lm is not None and not isinstance(lm, (DecodeLM, DecodeNNLM, DecodeRNNLM)):
+    search = [(cfg, name) for kind, cfg, name in _BEAM_SEARCH if isinstance(lm, kind)]
+    if not search:
         raise ValueError("decode_beam_batch: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM, a "
                          "ctc_fast.DecodeRNNLM or None")
+    config, name = search[0]
     if lm is not None and lm.sym_words.shape[0] < A:
         raise ValueError("decode_beam_batch: the LM maps %d symbols, the input has %d"
                          % (lm.sym_words.shape[0], A))
     Tb = np.ascontiguousarray(T_b, dtype=np.int32)
     off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(T_b)[:-1]]) if B else [], dtype=np.int64)
     sw = np.ascontiguousarray(lm.sym_words[:A] if lm is not None else np.zeros(A, np.int32), dtype=np.int32)
-    cfg = _sctc.BeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
-                           float(alpha), float(beta), lm.handle if lm is not None else None, _sctc.i32(sw))
+    cfg = config(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off), float(alpha),
+                 float(beta), lm.handle if lm is not None else None, _sctc.i32(sw))
     L = _sctc.lib()
-    if isinstance(lm, DecodeNNLM):
-        cfg = _sctc.NNBeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
-                                 float(alpha), float(beta), lm.handle, _sctc.i32(sw))
-        return _decode_launch(cfg, L.sctc_ctc_nnbeam_workspace_bytes, L.sctc_ctc_nnbeam_decode_batch, arrs, src, A,
-                              T_b, dt, nbest, "decode_beam_batch")
-    if isinstance(lm, DecodeRNNLM):
-        cfg = _sctc.RNNBeamConfig(B, int(A), dtype, int(beam), int(nbest), 0, int(A), _sctc.i32(Tb), _sctc.i64(off),
-                                  float(alpha), float(beta), lm.handle, _sctc.i32(sw))
-        return _decode_launch(cfg, L.sctc_ctc_rnnbeam_workspace_bytes, L.sctc_ctc_rnnbeam_decode_batch, arrs, src, A,
-                              T_b, dt, nbest, "decode_beam_batch")
-    return _decode_launch(cfg, L.sctc_ctc_beam_workspace_bytes, L.sctc_ctc_beam_decode_batch, arrs, src, A, T_b,
-                          dt, nbest, "decode_beam_batch")
+    return _decode_launch(cfg, getattr(L, "sctc_ctc_%s_workspace_bytes" % name),
+                          getattr(L, "sctc_ctc_%s_decode_batch" % name), arrs, src, A, T_b, dt, nbest,
+                          "decode_beam_batch")
 
 
-class DecodeLexicon(object):
+# decode_beam_batch by the type of its LM: the config class and the name of the entry points
+_BEAM_SEARCH = (((DecodeLM, type(None)), _sctc.BeamConfig, "beam"),
+                (DecodeNNLM, _sctc.NNBeamConfig, "nnbeam"),
+                (DecodeRNNLM, _sctc.RNNBeamConfig, "rnnbeam"))
+
+
+class DecodeLexicon(_DeviceHandle):
     """A lexicon on the device for :func:`decode_lexicon_beam_batch`: the prefix tree of
     ``words`` (plus ``specials``, tokens that are whole words) and the word-bigram LM ``arpa``
     (a :class:`decoder.lm.LM` or the path of an ARPA file), flattened and uploaded once.
@@ -519,6 +509,8 @@ class DecodeLexicon(object):
     chars: {token: symbol id} or the path of a ``token id`` file; words: a list or the path of a
     word list; space: the separator token or its symbol id; A: the alphabet size of the inputs
     (default: the largest symbol id + 1)."""
+
+    _destroy = "sctc_lexicon_destroy"
 
     def __init__(self, words, chars, arpa, space, specials=(), A=None):
         from decoder import decoder_utils, lm as lm_mod, prefixTree
@@ -555,17 +547,6 @@ class DecodeLexicon(object):
         _sctc.check(rc, "DecodeLexicon")
         self.handle = h
         self.device_bytes = int(_sctc.lib().sctc_lexicon_bytes(h))
-
-    def close(self):
-        if self.handle is not None and self.handle.value:
-            _sctc.lib().sctc_lexicon_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def decode_lexicon_beam_batch(logprobs, lengths=None, lexicon=None, beam=40, alpha=1.0, beta=0.0, nbest=1):

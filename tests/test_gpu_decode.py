@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import beam_model
+from tests.beam_trace import logsoftmax, peaked
 from tests.test_dataloader import write_shard
 
 pytestmark = pytest.mark.gpu
@@ -28,22 +29,6 @@ def beam_decoder(k):
     d.load_chars(CHARS)
     d.load_lm(lm_path(k))
     return d
-
-
-def logsoftmax(x):
-    m = x.max(axis=0, keepdims=True)
-    return x - m - np.log(np.exp(x - m).sum(axis=0, keepdims=True))
-
-
-def peaked(rs, A, T, sharp=6.0):
-    x = 1.5 * rs.randn(A, T)
-    t = 0
-    while t < T:
-        s = rs.randint(1, A) if rs.rand() < 0.6 else 0
-        r = rs.randint(1, 4)
-        x[s, t:t + r] += sharp
-        t += r
-    return logsoftmax(x)
 
 
 def assert_same(got_hyp, got_score, ref_hyp, ref_score, margin, what=""):

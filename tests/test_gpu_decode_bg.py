@@ -4,7 +4,6 @@ own results (tests/golden/decode_bg_ref.npz), the Python restatement (tests/lex_
 size, the lexicon property of every returned hypothesis, bigram terms read off forced paths, a beam
 with fewer live candidates than its width, the ABI corners the character decoder is held to, and
 runDecode.py --method bg."""
-import ctypes
 import os
 import pickle
 
@@ -12,24 +11,15 @@ import numpy as np
 import pytest
 
 from tests import lex_beam_model
+from tests.beam_harness import PATTERN, raw_decode
+from tests.beam_trace import logsoftmax, tol
 from tests.test_dataloader import write_shard
 from tests.test_decode_bg_cpu import ARPA, CHARS, GOLDEN, WORDS, fixture_lexicon
 
 pytestmark = pytest.mark.gpu
 
 NEG = float("-inf")
-PATTERN = 0xA5
 SPACE = 1
-
-
-def tol(x):
-    """the tolerance tests/test_gpu_decode.py:50 uses for this arithmetic"""
-    return 1e-6 * abs(x) + 1e-9
-
-
-def logsoftmax(x):
-    m = x.max(axis=0, keepdims=True)
-    return x - m - np.log(np.exp(x - m).sum(axis=0, keepdims=True))
 
 
 def objects():
@@ -295,51 +285,6 @@ def test_fewer_live_candidates_than_beam():
 
 # ---- 6. the ABI corners --------------------------------------------------------------------------
 
-def raw_decode(host, ld, A, T_b, frame_off, beam, nbest, dlex, alpha=0.8, beta=0.37, guard=0):
-    """sctc_ctc_lexbeam_decode_batch on a host matrix [rows][ld] as it stands.  With ``guard`` the
-    workspace (exactly sctc_ctc_lexbeam_workspace_bytes), ids, lengths and scores lie inside one
-    pattern-filled buffer, ``guard`` bytes apart; returns the bytes outside them."""
-    import torch
-    import _sctc
-    L = _sctc.lib()
-    B = len(T_b)
-    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
-    off = np.ascontiguousarray(frame_off, dtype=np.int64)
-    dtype = _sctc.F64 if host.dtype == np.float64 else _sctc.F32
-    cfg = _sctc.LexBeamConfig(B, A, dtype, beam, nbest, dlex.space, ld, _sctc.i32(Tb), _sctc.i64(off), alpha, beta,
-                              dlex.handle)
-    nbytes = L.sctc_ctc_lexbeam_workspace_bytes(ctypes.byref(cfg))
-    assert nbytes > 0
-    dev = torch.from_numpy(host).cuda()
-    n_ids = max(1, nbest * int(Tb.sum()))
-    sizes = [nbytes, 4 * n_ids, 4 * B * nbest, 8 * B * nbest]
-    g = max(256, (guard + 255) // 256 * 256)
-    offs, pos = [], g
-    for s in sizes:
-        offs.append(pos)
-        pos = (pos + s + g + 255) // 256 * 256
-    buf = torch.full((pos,), PATTERN, dtype=torch.uint8, device="cuda")
-    base = buf.data_ptr()
-    assert base % 256 == 0
-    ws, ids, lens, scores = (base + o for o in offs)
-    rc = L.sctc_ctc_lexbeam_decode_batch(ctypes.byref(cfg), dev.data_ptr(), ids, lens, scores, ws, nbytes,
-                                         _sctc.current_stream_ptr())
-    _sctc.check(rc, "raw_decode")
-    torch.cuda.synchronize()
-    out = buf.cpu().numpy()
-    inside = np.zeros(pos, dtype=bool)
-    for o, s in zip(offs, sizes):
-        inside[o:o + s] = True
-    ids_h = out[offs[1]:offs[1] + sizes[1]].view(np.int32)
-    lens_h = out[offs[2]:offs[2] + sizes[2]].view(np.int32).copy()
-    scores_h = out[offs[3]:offs[3] + sizes[3]].view(np.float64).reshape(B, nbest).copy()
-    hyps, b0 = [], 0
-    for b in range(B):
-        hyps.append([ids_h[b0 + n * Tb[b]:b0 + n * Tb[b] + lens_h[b * nbest + n]].copy() for n in range(nbest)])
-        b0 += nbest * int(Tb[b])
-    return hyps, scores_h, lens_h.reshape(B, nbest), out[~inside]
-
-
 def fixture_utts(rs, A, Ts, dt=np.float64):
     chars, _, _ = objects()
     _, _, lex, _ = fixture_device_lexicon(A, "large")
@@ -412,7 +357,7 @@ def test_ld_and_frame_offsets(dt):
         host[row:row + T_b[b], :A] = utts[b].T
         row += T_b[b]
     assert sorted(frame_off) != frame_off
-    hyps, scores, lens, _ = raw_decode(host, ld, A, T_b, frame_off, beam, nbest, dlex)
+    hyps, scores, lens, _, _ = raw_decode("lexbeam", host, ld, A, T_b, frame_off, beam, nbest, dlex, 0.8, 0.37)
     ph, ps = ctc_fast.decode_lexicon_beam_batch(utts, lexicon=dlex, beam=beam, alpha=0.8, beta=0.37, nbest=nbest)
     np.testing.assert_array_equal(scores, ps)
     assert not np.isnan(scores).any()
@@ -433,7 +378,8 @@ def test_exact_workspace_and_guarded_outputs(nbest):
     T_b = [u.shape[1] for u in utts]
     host = np.ascontiguousarray(np.concatenate([u.T for u in utts], axis=0))
     frame_off = np.concatenate([[0], np.cumsum(T_b)[:-1]])
-    hyps, scores, lens, outside = raw_decode(host, A, A, T_b, frame_off, beam, nbest, dlex, guard=4096)
+    hyps, scores, lens, outside, _ = raw_decode("lexbeam", host, A, A, T_b, frame_off, beam, nbest, dlex, 0.8, 0.37,
+                                                guard=4096)
     assert outside.size >= 5 * 4096 and np.all(outside == PATTERN)
     ph, ps = ctc_fast.decode_lexicon_beam_batch(utts, lexicon=dlex, beam=beam, alpha=0.8, beta=0.37, nbest=nbest)
     np.testing.assert_array_equal(scores, np.asarray(ps).reshape(len(utts), nbest))

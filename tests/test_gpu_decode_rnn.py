@@ -19,6 +19,7 @@ import pytest
 
 from tests import beam_model
 from tests import beam_trace as bt
+from tests.beam_harness import PATTERN, int_char_map, raw_decode, same_results
 from tests import rnn_lm_model as M
 
 pytestmark = pytest.mark.gpu
@@ -28,16 +29,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURE = os.path.join(GOLDEN, "lm_char_rnn.npz")
 CHARS = os.path.join(GOLDEN, "chars.txt")
 NEG = float("-inf")
-PATTERN = 0xA5
-
-
-def int_char_map():
-    chars = {}
-    with open(CHARS) as f:
-        for l in f:
-            t, i = l.split()
-            chars[int(i)] = t
-    return chars
 
 
 # name -> (seed, V, H); "fix" is tests/golden/lm_char_rnn.npz (V 37, H 64).  h40 is padded to 64, h1024
@@ -331,66 +322,6 @@ def test_end_to_end_against_float64_rows():
 
 # ---- 6. the C ABI below decode_beam_batch ------------------------------------------------------------------
 
-def raw_decode(host, ld, A, T_b, frame_off, beam, nbest, dlm, alpha=1.0, beta=0.0, guard=0):
-    """sctc_ctc_rnnbeam_decode_batch on a host matrix [rows][ld] as it stands.  With ``guard`` the
-    workspace (exactly sctc_ctc_rnnbeam_workspace_bytes, 256-byte aligned), ids, lengths and scores lie
-    inside one pattern-filled buffer, ``guard`` bytes apart; returns the bytes outside them."""
-    import torch
-    import _sctc
-    L = _sctc.lib()
-    B = len(T_b)
-    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
-    off = np.ascontiguousarray(frame_off, dtype=np.int64)
-    sw = np.ascontiguousarray(dlm.sym_words[:A], dtype=np.int32)
-    dtype = _sctc.F64 if host.dtype == np.float64 else _sctc.F32
-    cfg = _sctc.RNNBeamConfig(B, A, dtype, beam, nbest, 0, ld, _sctc.i32(Tb), _sctc.i64(off), alpha, beta,
-                              dlm.handle, _sctc.i32(sw))
-    nbytes = L.sctc_ctc_rnnbeam_workspace_bytes(ctypes.byref(cfg))
-    assert nbytes > 0
-    dev = torch.from_numpy(host).cuda()
-    n_ids = max(1, nbest * int(Tb.sum()))
-    sizes = [nbytes, 4 * n_ids, 4 * B * nbest, 8 * B * nbest]
-    g = max(256, (guard + 255) // 256 * 256)
-    offs, pos = [], g
-    for s in sizes:
-        offs.append(pos)
-        pos = (pos + s + g + 255) // 256 * 256
-    buf = torch.full((pos,), PATTERN, dtype=torch.uint8, device="cuda")
-    base = buf.data_ptr()
-    assert base % 256 == 0
-    ws, ids, lens, scores = (base + o for o in offs)
-    rc = L.sctc_ctc_rnnbeam_decode_batch(ctypes.byref(cfg), dev.data_ptr(), ids, lens, scores, ws, nbytes,
-                                         _sctc.current_stream_ptr())
-    _sctc.check(rc, "raw_decode")
-    torch.cuda.synchronize()
-    out = buf.cpu().numpy()
-    inside = np.zeros(pos, dtype=bool)
-    for o, s in zip(offs, sizes):
-        inside[o:o + s] = True
-    ids_h = out[offs[1]:offs[1] + sizes[1]].view(np.int32)
-    lens_h = out[offs[2]:offs[2] + sizes[2]].view(np.int32).copy()
-    scores_h = out[offs[3]:offs[3] + sizes[3]].view(np.float64).reshape(B, nbest).copy()
-    hyps, b0 = [], 0
-    for b in range(B):
-        hyps.append([ids_h[b0 + n * Tb[b]:b0 + n * Tb[b] + lens_h[b * nbest + n]].copy() for n in range(nbest)])
-        b0 += nbest * int(Tb[b])
-    return hyps, scores_h, lens_h.reshape(B, nbest), out[~inside], nbytes
-
-
-def same_results(h1, s1, h2, s2, nbest):
-    """scores and hypotheses array-equal; either side may list its hypotheses per utterance (raw_decode
-    always, decode_beam_batch with nbest > 1) or give the one hypothesis itself (nbest == 1)"""
-    np.testing.assert_array_equal(np.asarray(s1).reshape(-1), np.asarray(s2).reshape(-1))
-    assert len(h1) == len(h2)
-    for a, b in zip(h1, h2):
-        a = a if isinstance(a, list) else [a]
-        b = b if isinstance(b, list) else [b]
-        assert len(a) == len(b) == nbest
-        for x, y in zip(a, b):
-            assert np.asarray(x).ndim == 1 and np.asarray(y).ndim == 1
-            np.testing.assert_array_equal(x, y)
-
-
 @pytest.mark.parametrize("name", ["fix", "h1024"])
 def test_batch_composition_and_order(name):
     """an utterance decodes to the same bits alone, in a batch, and in the reversed batch"""
@@ -430,7 +361,7 @@ def test_ld_and_frame_offsets(dt):
         host[row:row + T_b[b], :A] = utts[b].T
         row += T_b[b]
     assert sorted(frame_off) != frame_off
-    hyps, scores, lens, _, _ = raw_decode(host, ld, A, T_b, frame_off, beam, nbest, dlm, alpha=0.8, beta=0.5)
+    hyps, scores, lens, _, _ = raw_decode("rnnbeam", host, ld, A, T_b, frame_off, beam, nbest, dlm, 0.8, 0.5)
     ph, ps = ctc_fast.decode_beam_batch(utts, beam=beam, alpha=0.8, beta=0.5, lm=dlm, nbest=nbest)
     assert not np.isnan(scores).any()
     same_results(hyps, scores, ph, ps, nbest)
@@ -449,7 +380,7 @@ def test_exact_workspace_and_guarded_outputs(name, nbest):
     T_b = [u.shape[1] for u in utts]
     host = np.ascontiguousarray(np.concatenate([u.T for u in utts], axis=0))
     frame_off = np.concatenate([[0], np.cumsum(T_b)[:-1]])
-    hyps, scores, lens, outside, nbytes = raw_decode(host, A, A, T_b, frame_off, beam, nbest, dlm, alpha=0.8,
+    hyps, scores, lens, outside, nbytes = raw_decode("rnnbeam", host, A, A, T_b, frame_off, beam, nbest, dlm, 0.8,
                                                      beta=0.5, guard=4096)
     assert outside.size >= 5 * 4096 and np.all(outside == PATTERN)
     lm = host_lm(name)

@@ -7,7 +7,6 @@ arbitrary frame offsets, an exact workspace, guarded output buffers, a batch lar
 
 tests/beam_trace.py has the rules of comparison.  Every precondition (cut gap, share of
 non-separated neighbours, one-kind ties) is asserted on the model before the GPU is touched."""
-import ctypes
 import os
 
 import numpy as np
@@ -15,21 +14,13 @@ import pytest
 
 from tests import beam_model
 from tests import beam_trace as bt
+from tests.beam_harness import PATTERN, int_char_map, raw_decode
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 NEG = float("-inf")
-
-
-def int_char_map():
-    chars = {}
-    with open(os.path.join(GOLDEN, "chars.txt")) as f:
-        for l in f:
-            t, i = l.split()
-            chars[int(i)] = t
-    return chars
 
 
 _LMS = {}
@@ -199,55 +190,6 @@ def test_twin_symbols_exact_ties(seed):
 
 # ---- the C ABI below decode_beam_batch -------------------------------------------------------
 
-PATTERN = 0xA5
-
-
-def raw_decode(host, ld, A, T_b, frame_off, beam, nbest, alpha=1.0, beta=0.0, dlm=None, guard=0):
-    """sctc_ctc_beam_decode_batch on a host matrix [rows][ld] as it stands.  With ``guard`` the
-    workspace (exactly sctc_ctc_beam_workspace_bytes, 256-byte aligned), ids, lengths and scores
-    lie inside one pattern-filled buffer, ``guard`` bytes apart; returns the bytes outside them."""
-    import torch
-    import _sctc
-    L = _sctc.lib()
-    B = len(T_b)
-    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
-    off = np.ascontiguousarray(frame_off, dtype=np.int64)
-    sw = np.ascontiguousarray(dlm.sym_words[:A] if dlm is not None else np.zeros(A, np.int32), dtype=np.int32)
-    dtype = _sctc.F64 if host.dtype == np.float64 else _sctc.F32
-    cfg = _sctc.BeamConfig(B, A, dtype, beam, nbest, 0, ld, _sctc.i32(Tb), _sctc.i64(off), alpha, beta,
-                           dlm.handle if dlm is not None else None, _sctc.i32(sw))
-    nbytes = L.sctc_ctc_beam_workspace_bytes(ctypes.byref(cfg))
-    assert nbytes > 0
-    dev = torch.from_numpy(host).cuda()
-    n_ids = max(1, nbest * int(Tb.sum()))
-    sizes = [nbytes, 4 * n_ids, 4 * B * nbest, 8 * B * nbest]
-    g = max(256, (guard + 255) // 256 * 256)
-    offs, pos = [], g
-    for s in sizes:
-        offs.append(pos)
-        pos = (pos + s + g + 255) // 256 * 256
-    buf = torch.full((pos,), PATTERN, dtype=torch.uint8, device="cuda")
-    base = buf.data_ptr()
-    assert base % 256 == 0
-    ws, ids, lens, scores = (base + o for o in offs)
-    rc = L.sctc_ctc_beam_decode_batch(ctypes.byref(cfg), dev.data_ptr(), ids, lens, scores, ws, nbytes,
-                                      _sctc.current_stream_ptr())
-    _sctc.check(rc, "raw_decode")
-    torch.cuda.synchronize()
-    out = buf.cpu().numpy()
-    inside = np.zeros(pos, dtype=bool)
-    for o, s in zip(offs, sizes):
-        inside[o:o + s] = True
-    ids_h = out[offs[1]:offs[1] + sizes[1]].view(np.int32)
-    lens_h = out[offs[2]:offs[2] + sizes[2]].view(np.int32).copy()
-    scores_h = out[offs[3]:offs[3] + sizes[3]].view(np.float64).reshape(B, nbest).copy()
-    hyps, b0 = [], 0
-    for b in range(B):
-        hyps.append([ids_h[b0 + n * Tb[b]:b0 + n * Tb[b] + lens_h[b * nbest + n]].copy() for n in range(nbest)])
-        b0 += nbest * int(Tb[b])
-    return hyps, scores_h, lens_h.reshape(B, nbest), out[~inside]
-
-
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
 def test_ld_and_frame_offsets(dt):
     """ld > A with NaN in the padding columns, utterances in shuffled order with NaN-filled gaps"""
@@ -268,7 +210,7 @@ def test_ld_and_frame_offsets(dt):
         host[row:row + T_b[b], :A] = utts[b].T
         row += T_b[b]
     assert sorted(frame_off) != frame_off
-    hyps, scores, lens, _ = raw_decode(host, ld, A, T_b, frame_off, beam, nbest, alpha=0.8, beta=0.5, dlm=dlm)
+    hyps, scores, lens, _, _ = raw_decode("beam", host, ld, A, T_b, frame_off, beam, nbest, dlm, 0.8, 0.5)
     ph, ps = ctc_fast.decode_beam_batch(utts, beam=beam, alpha=0.8, beta=0.5, lm=dlm, nbest=nbest)
     np.testing.assert_array_equal(scores, ps)
     assert not np.isnan(scores).any()
@@ -290,8 +232,8 @@ def test_exact_workspace_and_guarded_outputs(lm, nbest):
     T_b = [u.shape[1] for u in utts]
     host = np.ascontiguousarray(np.concatenate([u.T for u in utts], axis=0))
     frame_off = np.concatenate([[0], np.cumsum(T_b)[:-1]])
-    hyps, scores, lens, outside = raw_decode(host, A, A, T_b, frame_off, beam, nbest, alpha=0.8, beta=0.5,
-                                             dlm=dlm, guard=4096)
+    hyps, scores, lens, outside, _ = raw_decode("beam", host, A, A, T_b, frame_off, beam, nbest, dlm, 0.8, 0.5,
+                                                guard=4096)
     assert outside.size >= 5 * 4096 and np.all(outside == PATTERN)
     ph, ps = ctc_fast.decode_beam_batch(utts, beam=beam, alpha=0.8, beta=0.5, lm=dlm, nbest=nbest)
     np.testing.assert_array_equal(scores, np.asarray(ps).reshape(len(utts), nbest))
