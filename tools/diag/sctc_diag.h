@@ -3,8 +3,8 @@
  * the kernels of libsctc_hip.so.  NOT part of the drop-in boundary (include/sctc.h): nothing in
  * stanford-ctc_amd/ loads this library; tests/gpu_diag.py, bench.py's "sustained peak" note and
  * __graft_entry__.smoke() do.  These entry points allocate (and free) their own scratch memory.
- * The library links against libsctc_hip.so for one purpose: sctc_diag_gemm below, the tests' door to the
- * product's own GEMM launcher.
+ * The library links against libsctc_hip.so for one purpose: the tests' doors below to the product's own GEMM
+ * launcher (sctc_diag_gemm) and to its internal elementwise launchers.
  */
 #ifndef SCTC_DIAG_H_
 #define SCTC_DIAG_H_
@@ -84,6 +84,24 @@ int sctc_diag_gemm(const sctc_diag_gemm_args* args, void* stream);
 /* sctc::gemm_plan_splits: the split-K count the product picks for this shape (through *splits) and the
  * workspace floats it needs (0 when *splits == 1) */
 int64_t sctc_diag_gemm_plan_splits(int32_t M, int32_t N, int32_t K, int32_t prec, int32_t in16, int32_t* splits);
+
+/* ---- test-only door to the internal launchers of stanford-ctc_amd/csrc/elementwise.h (elementwise_entry.hip;
+ * tests/test_gpu_elementwise.py): each entry passes its arguments to the sctc::launch_* function of libsctc_hip.so of
+ * the same name and returns its code; the message of an error is in the PRODUCT library's sctc_last_error().
+ * add / cvt16 / add16 move float4 groups: 16-byte aligned pointers, n a multiple of 4.  Nullable: both outputs of
+ * cvt16, every output of add16, both shadows of gather_rows16. */
+int sctc_diag_gather_rows(float* dst, int64_t ldd, const float* src, int64_t lds, const int32_t* idx, int64_t rows,
+                          int32_t cols, void* stream);
+int sctc_diag_scatter_rows(float* dst, int64_t ldd, const float* src, int64_t lds, const int32_t* idx, int64_t rows,
+                           int32_t cols, void* stream);
+int sctc_diag_add(float* out, const float* a, const float* b, int64_t n, void* stream);
+int sctc_diag_cvt16(const float* src, uint16_t* dst_f16, uint16_t* dst_bf16, int64_t n, void* stream);
+int sctc_diag_add16(float* out, const float* a, const float* b, uint16_t* o_f16, uint16_t* o_bf16, uint16_t* a_bf16,
+                    uint16_t* b_bf16, int64_t n, void* stream);
+int sctc_diag_transpose_bf16(const float* src, int64_t ld_src, uint16_t* dst, int64_t ld_dst, int32_t rows,
+                             int32_t cols, void* stream);
+int sctc_diag_gather_rows16(float* dst, uint16_t* d_f16, uint16_t* d_bf16, int64_t ldd, const float* src, int64_t lds,
+                            const int32_t* idx, int64_t rows, int32_t cols, void* stream);
 
 #ifdef __cplusplus
 }

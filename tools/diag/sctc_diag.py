@@ -51,5 +51,14 @@ def lib():
         L.sctc_diag_gemm.argtypes = [ctypes.POINTER(GemmArgs), ctypes.c_void_p]
         L.sctc_diag_gemm_plan_splits.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)]
         L.sctc_diag_gemm_plan_splits.restype = ctypes.c_int64
+        # the internal launchers of csrc/elementwise.h (elementwise_entry.hip); pointers as plain addresses
+        vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+        L.sctc_diag_gather_rows.argtypes = [vp, i64, vp, i64, vp, i64, i32, vp]
+        L.sctc_diag_scatter_rows.argtypes = [vp, i64, vp, i64, vp, i64, i32, vp]
+        L.sctc_diag_add.argtypes = [vp, vp, vp, i64, vp]
+        L.sctc_diag_cvt16.argtypes = [vp, vp, vp, i64, vp]
+        L.sctc_diag_add16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        L.sctc_diag_transpose_bf16.argtypes = [vp, i64, vp, i64, i32, i32, vp]
+        L.sctc_diag_gather_rows16.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32, vp]
         _lib = L
     return _lib
