@@ -257,14 +257,12 @@ static size_t carve(const sctc_brnn_config* c, const Dims& d, sctc_brnn* h, void
     int32_t* d_idx_hi = ar.take<int32_t>(F);
     int32_t* d_xbase = ar.take<int32_t>(F);
     int32_t* d_perm = ar.take<int32_t>(Bm);
-    // CTC workspace, worst case: every frame carries a CTC_LP_MAX-wide lattice row (x2)
+    // CTC workspace, worst case: every frame carries a CTC_LP_MAX-wide lattice row (x2) and a label, with
+    // ctc_generic.hip's row scratch
     size_t ctc_bytes = 0;
     void* ctc_ws = nullptr;
     if (c->train) {
-        ctc_bytes = align256(sizeof(CtcUtt) * Bm) + align256(sizeof(int32_t) * (2 * F + (int64_t)Bm * (d.A + 1))) +
-                    align256(sizeof(double) * 2 * Bm) + align256(sizeof(int32_t) * 2 * Bm) +
-                    2 * align256(sizeof(double) * F * CTC_LP_MAX) +
-                    align256(sizeof(double) * 4 * (size_t)Bm * CTC_LP_MAX);   // ctc_generic.hip's row scratch
+        ctc_bytes = ctc_layout_slices(CTC_GENERIC, Bm, d.A, F, F * CTC_LP_MAX, CTC_LP_MAX, 8).bytes;
         ctc_ws = ar.take<char>(ctc_bytes);
     }
     // split-K partials: worst case over the weight-gradient GEMMs
@@ -1281,9 +1279,7 @@ int sctc_brnn_ctc_workspace_bytes(sctc_brnn_t h, const sctc_minibatch* mb, size_
     SCTC_CHECK_ARG(h && mb && needed, "brnn_ctc_workspace_bytes: null argument");
     SCTC_CHECK_ARG(h->cfg.train, "brnn_ctc_workspace_bytes: the model was created with train = 0 (no CTC)");
     SCTC_CHECK_ARG(mb->B >= 1 && mb->B <= h->cfg.max_utts && mb->T_b && mb->U_b, "brnn_ctc_workspace_bytes: bad minibatch");
-    CtcPlan plan;
-    SCTC_TRY(ctc_make_plan(mb->B, h->A, 0, SCTC_F32, mb->T_b, mb->U_b, &plan));
-    *needed = plan.bytes;
+    SCTC_TRY(ctc_workspace_bytes(mb->B, h->A, 0, SCTC_F32, mb->T_b, mb->U_b, needed));
     if (reserved) *reserved = h->ctc_ws_ext ? h->ctc_ws_ext_bytes : h->ctc_ws_bytes;
     return SCTC_OK;
 }

@@ -75,13 +75,8 @@ namespace sctc {
 // later trims (1.100 / 1.107 ms; tools/ctc_form_sweep.py).
 template <typename RI, typename ST, int K, int NA, bool HELP>
 struct FusedDiet {
-#ifdef SCTC_FUSED_NO_DIET       // A/B build (tools/build_variant.sh nodiet ctc_fused.hip -DSCTC_FUSED_NO_DIET)
-    static constexpr bool possible = false;
-#else
-    static constexpr bool possible = !HELP && NA == 1 && K <= 4 && sizeof(RI) == 4 && sizeof(ST) == 4;
-#endif
+    static constexpr bool possible = ctc_fused_diet_exists(sizeof(RI), sizeof(ST), K, NA, HELP);    // ctc_plan.h
 };
-static constexpr int FUSED_DIET_MIN_B = 1025;
 
 template <typename RI, typename ST, int K, int NA, bool HELP, bool DIET = false>
 __global__ __launch_bounds__(HELP ? 384 : 128) __attribute__((amdgpu_waves_per_eu(DIET ? 3 : 1, 8)))
@@ -905,87 +900,68 @@ void ctc_fused_kernel(CtcFusedArgs<RI> p)
     }
 }
 
-// ---------------------------------------------------------------- launcher
+// ---------------------------------------------------------------- launcher: the plan's (store, K, NA, help, diet) -> one instantiation
 
-template <typename RI, typename ST, int K, int NA, bool HELP>
+template <typename RI, typename ST, int K, int NA, bool HELP, bool DIET>
 static int launch_fused_one(const CtcFusedArgs<RI>& a, int B, hipStream_t stream)
 {
-    dim3 grid(B), block(HELP ? 384 : 128);
-    // 8 states per lane with helper waves: the 64 KiB ring is dynamic LDS (static + dynamic > 64 KiB needs the attribute)
-    const size_t dyn = (HELP && K == 8) ? sizeof(double) * 2 * 2 * 4 * 64 * K : 0;
-    if (dyn) {
-        static std::once_flag once;     // one per instantiation
-        static hipError_t attr = hipSuccess;
-        std::call_once(once, [&] {
-            attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_fused_kernel<RI, ST, K, NA, HELP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        });
-        SCTC_HIP_TRY(attr);
-    }
-    if constexpr (FusedDiet<RI, ST, K, NA, HELP>::possible) {
-        const char* dz = getenv("SCTC_CTC_DIET_MIN_B");      // tests / A/B: the dieted form from this many utterances on
-        if (B >= (dz ? atoi(dz) : FUSED_DIET_MIN_B)) {
-            hipLaunchKernelGGL((ctc_fused_kernel<RI, ST, K, NA, HELP, true>), grid, block, dyn, stream, a);
-            SCTC_HIP_TRY(hipGetLastError());
-            return SCTC_OK;
+    if constexpr ((HELP && !ctc_fused_help_exists(sizeof(ST), K, NA)) || (DIET && !FusedDiet<RI, ST, K, NA, HELP>::possible)) {
+        return set_error(SCTC_ERR_ARG, "ctc: no fused kernel with helpers = %d, diet = %d for K=%d, NA=%d, %d-byte rows", (int)HELP,
+                         (int)DIET, K, NA, (int)sizeof(ST));
+    } else {
+        dim3 grid(B), block(HELP ? 384 : 128);
+        // 8 states per lane with helper waves: the 64 KiB ring is dynamic LDS (static + dynamic > 64 KiB needs the attribute)
+        const size_t dyn = (HELP && K == 8) ? sizeof(double) * 2 * 2 * 4 * 64 * K : 0;
+        if (dyn) {
+            static std::once_flag once;     // one per instantiation
+            static hipError_t attr = hipSuccess;
+            std::call_once(once, [&] {
+                attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_fused_kernel<RI, ST, K, NA, HELP, DIET>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+            });
+            SCTC_HIP_TRY(attr);
         }
+        hipLaunchKernelGGL((ctc_fused_kernel<RI, ST, K, NA, HELP, DIET>), grid, block, dyn, stream, a);
+        SCTC_HIP_TRY(hipGetLastError());
+        return SCTC_OK;
     }
-    hipLaunchKernelGGL((ctc_fused_kernel<RI, ST, K, NA, HELP>), grid, block, dyn, stream, a);
-    SCTC_HIP_TRY(hipGetLastError());
-    return SCTC_OK;
 }
 
-template <typename RI, typename ST, int K, bool HELP>
-static int launch_fused_kh(const CtcFusedArgs<RI>& a, int B, int NA, hipStream_t stream)
+template <typename RI, typename ST, int K, int NA>
+static int launch_fused_na(const CtcFusedArgs<RI>& a, const CtcPlan& plan, hipStream_t stream)
 {
-    if constexpr (!(HELP && K == 8 && sizeof(ST) == 8)) {
-        if (NA == 1) return launch_fused_one<RI, ST, K, 1, HELP>(a, B, stream);
-    }
-    if constexpr (!(HELP && K == 8)) {
-        if (NA == 2) return launch_fused_one<RI, ST, K, 2, HELP>(a, B, stream);
-    }
-    if constexpr (!HELP) return launch_fused_one<RI, ST, K, 4, false>(a, B, stream);
-    return set_error(SCTC_ERR_ARG, "ctc: no helper form for %d probability registers per frame", NA);
+    if (plan.help) return plan.diet ? launch_fused_one<RI, ST, K, NA, true, true>(a, plan.B, stream) : launch_fused_one<RI, ST, K, NA, true, false>(a, plan.B, stream);
+    return plan.diet ? launch_fused_one<RI, ST, K, NA, false, true>(a, plan.B, stream) : launch_fused_one<RI, ST, K, NA, false, false>(a, plan.B, stream);
 }
 
-template <typename RI, typename ST, int K>
-static int launch_fused_k(const CtcFusedArgs<RI>& a, int B, int NA, hipStream_t stream)
+template <typename RI, typename ST>
+static int launch_fused_st(const CtcFusedArgs<RI>& a, const CtcPlan& plan, hipStream_t stream)
 {
-    // Helper waves (six waves per utterance) while the batch leaves SIMDs idle; beyond SCTC_CTC_HELPER_MAX_B
-    // utterances (default 256: one six-wave workgroup per CU) the two-wave form keeps more utterances resident
-    // (four workgroups per CU; 4096 utterances of the cfg-3 shape: 3.5 ms against 4.5).  Alphabets
-    // of more than 128 symbols (four probability registers per frame) always take the two-wave form: the helper's
-    // register budget is 256.  SCTC_CTC_HELPER=0 / 1 forces one form (A/B, tests).
-    const char* hz = getenv("SCTC_CTC_HELPER");
-    const char* mz = getenv("SCTC_CTC_HELPER_MAX_B");
-    const int max_b = mz ? atoi(mz) : 256;
-    // (8 states per lane: helpers only for alphabets of up to 64 symbols -- the register budget again)
-    // and for the 32-bit row store -- the register budget again)
-    const bool help = (K == 8 ? (NA == 1 && sizeof(ST) == 4) : NA <= 2) && (hz ? atoi(hz) != 0 : B <= max_b);
-    if (help) return launch_fused_kh<RI, ST, K, true>(a, B, NA, stream);
-    return launch_fused_kh<RI, ST, K, false>(a, B, NA, stream);
+    switch (plan.K * 10 + plan.NA) {
+        case 21: return launch_fused_na<RI, ST, 2, 1>(a, plan, stream);
+        case 22: return launch_fused_na<RI, ST, 2, 2>(a, plan, stream);
+        case 24: return launch_fused_na<RI, ST, 2, 4>(a, plan, stream);
+        case 41: return launch_fused_na<RI, ST, 4, 1>(a, plan, stream);
+        case 42: return launch_fused_na<RI, ST, 4, 2>(a, plan, stream);
+        case 44: return launch_fused_na<RI, ST, 4, 4>(a, plan, stream);
+        case 81: return launch_fused_na<RI, ST, 8, 1>(a, plan, stream);
+        case 82: return launch_fused_na<RI, ST, 8, 2>(a, plan, stream);
+        case 84: return launch_fused_na<RI, ST, 8, 4>(a, plan, stream);
+    }
+    return set_error(SCTC_ERR_ARG, "ctc: no fused kernel for K=%d, NA=%d", plan.K, plan.NA);
 }
 
 template <typename RI>
-int launch_ctc_fused(const CtcFusedArgs<RI>& a, int B, int K, int store_bytes, hipStream_t stream)
+int launch_ctc_fused(const CtcFusedArgs<RI>& a, const CtcPlan& plan, hipStream_t stream)
 {
-    const int NA = a.A <= 64 ? 1 : (a.A <= 128 ? 2 : 4);
     if constexpr (sizeof(RI) == 4) {
-        if (store_bytes == 4) {
-            if (K == 2) return launch_fused_k<RI, uint32_t, 2>(a, B, NA, stream);
-            if (K == 4) return launch_fused_k<RI, uint32_t, 4>(a, B, NA, stream);
-            if (K == 8) return launch_fused_k<RI, uint32_t, 8>(a, B, NA, stream);
-        }
+        if (plan.store_bytes == 4) return launch_fused_st<RI, uint32_t>(a, plan, stream);
     }
-    if (store_bytes == 8) {
-        if (K == 2) return launch_fused_k<RI, double, 2>(a, B, NA, stream);
-        if (K == 4) return launch_fused_k<RI, double, 4>(a, B, NA, stream);
-        if (K == 8) return launch_fused_k<RI, double, 8>(a, B, NA, stream);
-    }
-    return set_error(SCTC_ERR_ARG, "ctc: no fused kernel for K=%d, %d-byte rows", K, store_bytes);
+    if (plan.store_bytes == 8) return launch_fused_st<RI, double>(a, plan, stream);
+    return set_error(SCTC_ERR_ARG, "ctc: no fused kernel for %d-byte rows", plan.store_bytes);
 }
 
-template int launch_ctc_fused<float>(const CtcFusedArgs<float>&, int, int, int, hipStream_t);
-template int launch_ctc_fused<double>(const CtcFusedArgs<double>&, int, int, int, hipStream_t);
+template int launch_ctc_fused<float>(const CtcFusedArgs<float>&, const CtcPlan&, hipStream_t);
+template int launch_ctc_fused<double>(const CtcFusedArgs<double>&, const CtcPlan&, hipStream_t);
 
 }  // namespace sctc

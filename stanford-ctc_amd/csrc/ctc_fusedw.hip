@@ -25,7 +25,7 @@
 //   * skip (a zero band sum, :45 / :75) in either direction takes back every gradient row: the two workgroups
 //     exchange their verdicts once more at the end.
 //
-// Where it is used (ctc_make_plan, capi_ctc.hip): from 18 utterances on (24 for rows of up to 1024 states) -- below that the
+// Where it is used (ctc_plan, ctc_plan.h): from 18 utterances on (24 for rows of up to 1024 states) -- below that the
 // lattice + grad pair is faster, because its gradient kernel runs on the CUs a few recursion workgroups leave idle, while
 // here the gradient rows cost the recursion waves their own issue slots (cfg-5 shape: 8 utterances 5.40 against 4.95 ms,
 // 24: 5.48 / 5.82, 128: 6.0 / 15); a fifth of the HBM traffic and a tenth of the workspace at every size.
@@ -42,8 +42,8 @@
 
 namespace sctc {
 
-// sync words per utterance (zeroed by the launcher): [0..1] phase 0 finished (1 + skip) per direction, [2..3] all done
-static constexpr int FUSEDW_SYNC_WORDS = 4;
+// FUSEDW_SYNC_WORDS (ctc_plan.h) sync words per utterance, zeroed by the launcher: [0..1] phase 0 finished (1 + skip) per
+// direction, [2..3] all done
 
 template <typename RI, typename ST, int K, int NA, int W>
 __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, int B)
@@ -614,7 +614,7 @@ __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, 
     }
 }
 
-// ---------------------------------------------------------------- launcher
+// ---------------------------------------------------------------- launcher: the plan's (store, K, W, NA) -> one instantiation
 
 template <typename RI, typename ST, int K, int NA, int W>
 static int launch_fusedw_one(const CtcFusedArgs<RI>& a, int B, hipStream_t stream)
@@ -637,38 +637,36 @@ static int launch_fusedw_one(const CtcFusedArgs<RI>& a, int B, hipStream_t strea
 }
 
 template <typename RI, typename ST, int K, int W>
-static int launch_fusedw_k(const CtcFusedArgs<RI>& a, int B, hipStream_t stream)
+static int launch_fusedw_k(const CtcFusedArgs<RI>& a, const CtcPlan& plan, hipStream_t stream)
 {
-    const int NA = a.A <= 64 ? 1 : (a.A <= 128 ? 2 : 4);
-    if (NA == 1) return launch_fusedw_one<RI, ST, K, 1, W>(a, B, stream);
-    if (NA == 2) return launch_fusedw_one<RI, ST, K, 2, W>(a, B, stream);
-    return launch_fusedw_one<RI, ST, K, 4, W>(a, B, stream);
+    if (plan.NA == 1) return launch_fusedw_one<RI, ST, K, 1, W>(a, plan.B, stream);
+    if (plan.NA == 2) return launch_fusedw_one<RI, ST, K, 2, W>(a, plan.B, stream);
+    if (plan.NA == 4) return launch_fusedw_one<RI, ST, K, 4, W>(a, plan.B, stream);
+    return set_error(SCTC_ERR_ARG, "ctc: no wide fused kernel for NA=%d", plan.NA);
 }
 
 template <typename RI, typename ST>
-static int launch_fusedw_st(const CtcFusedArgs<RI>& a, int B, int K, int W, hipStream_t stream)
+static int launch_fusedw_st(const CtcFusedArgs<RI>& a, const CtcPlan& plan, hipStream_t stream)
 {
-    if (W == 4 && K == 2) return launch_fusedw_k<RI, ST, 2, 4>(a, B, stream);
-    if (W == 4 && K == 4) return launch_fusedw_k<RI, ST, 4, 4>(a, B, stream);
-    if (W == 8 && K == 2) return launch_fusedw_k<RI, ST, 2, 8>(a, B, stream);
-    if (W == 8 && K == 4) return launch_fusedw_k<RI, ST, 4, 8>(a, B, stream);
+    const int K = plan.K, W = plan.W;
+    if (W == 4 && K == 2) return launch_fusedw_k<RI, ST, 2, 4>(a, plan, stream);
+    if (W == 4 && K == 4) return launch_fusedw_k<RI, ST, 4, 4>(a, plan, stream);
+    if (W == 8 && K == 2) return launch_fusedw_k<RI, ST, 2, 8>(a, plan, stream);
+    if (W == 8 && K == 4) return launch_fusedw_k<RI, ST, 4, 8>(a, plan, stream);
     return set_error(SCTC_ERR_ARG, "ctc: no wide fused kernel for K=%d, W=%d", K, W);
 }
 
-// the flag words and, behind them, 64 doubles of dump area (stores of lanes / frames that have nothing to store)
-size_t ctc_fusedw_sync_bytes(int B) { return sizeof(uint32_t) * FUSEDW_SYNC_WORDS * (size_t)((B + 1) & ~1) + 64 * sizeof(double); }
-
 template <typename RI>
-int launch_ctc_fusedw(const CtcFusedArgs<RI>& a, int B, int K, int W, int store_bytes, hipStream_t stream)
+int launch_ctc_fusedw(const CtcFusedArgs<RI>& a, const CtcPlan& plan, hipStream_t stream)
 {
     if constexpr (sizeof(RI) == 4) {
-        if (store_bytes == 4) return launch_fusedw_st<RI, uint32_t>(a, B, K, W, stream);
+        if (plan.store_bytes == 4) return launch_fusedw_st<RI, uint32_t>(a, plan, stream);
     }
-    if (store_bytes == 8) return launch_fusedw_st<RI, double>(a, B, K, W, stream);
-    return set_error(SCTC_ERR_ARG, "ctc: no wide fused kernel for %d-byte rows", store_bytes);
+    if (plan.store_bytes == 8) return launch_fusedw_st<RI, double>(a, plan, stream);
+    return set_error(SCTC_ERR_ARG, "ctc: no wide fused kernel for %d-byte rows", plan.store_bytes);
 }
 
-template int launch_ctc_fusedw<float>(const CtcFusedArgs<float>&, int, int, int, int, hipStream_t);
-template int launch_ctc_fusedw<double>(const CtcFusedArgs<double>&, int, int, int, int, hipStream_t);
+template int launch_ctc_fusedw<float>(const CtcFusedArgs<float>&, const CtcPlan&, hipStream_t);
+template int launch_ctc_fusedw<double>(const CtcFusedArgs<double>&, const CtcPlan&, hipStream_t);
 
 }  // namespace sctc

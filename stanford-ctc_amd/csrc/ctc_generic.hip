@@ -243,16 +243,16 @@ int launch_softmax_rows_generic(const float* x, float* y, int64_t rows, int A, i
 }
 
 template <typename RI>
-int launch_ctc_generic(const CtcLatticeArgs<RI>& la, const CtcGradArgs<RI>& ga, int B, int max_T, hipStream_t stream)
+int launch_ctc_generic(const CtcLatticeArgs<RI>& la, const CtcGradArgs<RI>& ga, const CtcPlan& plan, hipStream_t stream)
 {
-    hipLaunchKernelGGL(ctc_lattice_generic_kernel<RI>, dim3(B, 2), dim3(GEN_NT), 0, stream, la);
+    hipLaunchKernelGGL(ctc_lattice_generic_kernel<RI>, dim3(plan.B, 2), dim3(GEN_NT), 0, stream, la);
     SCTC_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ctc_grad_generic_kernel<RI>, dim3(max_T, B), dim3(256), 0, stream, ga);
+    hipLaunchKernelGGL(ctc_grad_generic_kernel<RI>, dim3(plan.max_T, plan.B), dim3(256), 0, stream, ga);
     SCTC_HIP_TRY(hipGetLastError());
     return SCTC_OK;
 }
 
-template int launch_ctc_generic<float>(const CtcLatticeArgs<float>&, const CtcGradArgs<float>&, int, int, hipStream_t);
-template int launch_ctc_generic<double>(const CtcLatticeArgs<double>&, const CtcGradArgs<double>&, int, int, hipStream_t);
+template int launch_ctc_generic<float>(const CtcLatticeArgs<float>&, const CtcGradArgs<float>&, const CtcPlan&, hipStream_t);
+template int launch_ctc_generic<double>(const CtcLatticeArgs<double>&, const CtcGradArgs<double>&, const CtcPlan&, hipStream_t);
 
 }  // namespace sctc

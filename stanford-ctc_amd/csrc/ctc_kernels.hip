@@ -705,7 +705,8 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(CtcGradArgs<RI> p)
     }
 }
 
-// ---------------------------------------------------------------- launchers
+// ---------------------------------------------------------------- launchers: the plan's (K, W, NA, lazy) / NB -> one instantiation
+// (the lattice shapes and their measurements: ctc_lattice_shape, ctc_plan.h)
 
 template <typename RI, int K, int W>
 static int launch_lattice_k(const CtcLatticeArgs<RI>& a, int B, int NA, int lazy, hipStream_t stream)
@@ -727,40 +728,12 @@ static int launch_lattice_k(const CtcLatticeArgs<RI>& a, int B, int NA, int lazy
     return SCTC_OK;
 }
 
-// Lattice shape for label rows of up to max_L = 2U+1 states: K states per lane, W waves per
-// (utterance, pass).  Up to 256 states one wave holds everything (no cross-wave traffic); longer
-// rows are spread over 4 waves so that a frame costs K/4 as many dependent float64 operations, and
-// rows of more than 1024 states over 8 waves (two per SIMD): at T = 8000 / U = 800 a frame costs 0.65
-// instead of 0.73 us with 4 states per lane instead of 8 (round 3; 16 waves x 2 states: 1.2 us --
-// four waves per SIMD meet at the frame's barrier; 8 waves x 2 states for 513..1024 states: 2-4 %
-// slower than 4 waves x 4).  Costs and gradients agree to all printed digits
-// between the shapes (tests/gpu_ctc_shape.py); the band sum is taken in another order, so the last
-// bits of a lattice may differ from one shape to the other.
-int ctc_lattice_shape(int max_L, int* waves)
-{
-    const char* force = getenv("SCTC_CTC_WAVES");   // diagnostics: 1 / 4 / 8
-    const int fw = force ? atoi(force) : 0;
-    if ((fw == 0 && max_L <= 256) || fw == 1) {
-        *waves = 1;
-        for (int k = 2; k <= 32; k *= 2)
-            if (max_L <= 64 * k) return k;
-        return 0;
-    }
-    if (fw == 8 || (fw == 0 && max_L > 1024)) {
-        *waves = 8;
-        return max_L <= 1024 ? 2 : (max_L <= 2048 ? 4 : 0);
-    }
-    *waves = 4;
-    for (int k = 2; k <= 8; k *= 2)
-        if (max_L <= 256 * k) return k;
-    return 0;
-}
-
 template <typename RI>
-int launch_ctc_lattice(const CtcLatticeArgs<RI>& a, int B, int K, int W, int lazy, hipStream_t stream)
+int launch_ctc_lattice(const CtcLatticeArgs<RI>& a, const CtcPlan& plan, hipStream_t stream)
 {
     using R = RI;
-    const int NA = a.A <= 64 ? 1 : (a.A <= 128 ? 2 : 4);
+    const int B = plan.B, K = plan.K, W = plan.W, NA = plan.NA, lazy = plan.lazy;
+    if (NA != 1 && NA != 2 && NA != 4) return set_error(SCTC_ERR_ARG, "ctc: no lattice kernel for NA=%d", NA);
     if (W == 8) {
         switch (K) {
             case 2: return launch_lattice_k<R, 2, 8>(a, B, NA, lazy, stream);
@@ -773,7 +746,7 @@ int launch_ctc_lattice(const CtcLatticeArgs<RI>& a, int B, int K, int W, int laz
             case 4: return launch_lattice_k<R, 4, 4>(a, B, NA, lazy, stream);
             case 8: return launch_lattice_k<R, 8, 4>(a, B, NA, lazy, stream);
         }
-    } else {
+    } else if (W == 1) {
         switch (K) {
             case 2: return launch_lattice_k<R, 2, 1>(a, B, NA, lazy, stream);
             case 4: return launch_lattice_k<R, 4, 1>(a, B, NA, lazy, stream);
@@ -800,18 +773,19 @@ static int launch_ctc_grad_nb(const CtcGradArgs<R>& a, int B, int max_T, hipStre
 }
 
 template <typename R>
-int launch_ctc_grad(const CtcGradArgs<R>& a, int B, int max_T, hipStream_t stream)
+int launch_ctc_grad(const CtcGradArgs<R>& a, const CtcPlan& plan, hipStream_t stream)
 {
-    // (short rows: four slices per trip -- the clamped loads of slices beyond the row are not free: 4096 utterances of
-    // 201 states took 7.3 instead of 5.0 ms with sixteen)
-    if (a.lp <= 256) return launch_ctc_grad_nb<R, 4>(a, B, max_T, stream);
-    if (a.lp <= 512) return launch_ctc_grad_nb<R, 8>(a, B, max_T, stream);
-    return launch_ctc_grad_nb<R, 16>(a, B, max_T, stream);
+    switch (plan.NB) {
+        case 4: return launch_ctc_grad_nb<R, 4>(a, plan.B, plan.max_T, stream);
+        case 8: return launch_ctc_grad_nb<R, 8>(a, plan.B, plan.max_T, stream);
+        case 16: return launch_ctc_grad_nb<R, 16>(a, plan.B, plan.max_T, stream);
+    }
+    return set_error(SCTC_ERR_ARG, "ctc: no gradient kernel for NB=%d", plan.NB);
 }
 
-template int launch_ctc_lattice<float>(const CtcLatticeArgs<float>&, int, int, int, int, hipStream_t);
-template int launch_ctc_lattice<double>(const CtcLatticeArgs<double>&, int, int, int, int, hipStream_t);
-template int launch_ctc_grad<float>(const CtcGradArgs<float>&, int, int, hipStream_t);
-template int launch_ctc_grad<double>(const CtcGradArgs<double>&, int, int, hipStream_t);
+template int launch_ctc_lattice<float>(const CtcLatticeArgs<float>&, const CtcPlan&, hipStream_t);
+template int launch_ctc_lattice<double>(const CtcLatticeArgs<double>&, const CtcPlan&, hipStream_t);
+template int launch_ctc_grad<float>(const CtcGradArgs<float>&, const CtcPlan&, hipStream_t);
+template int launch_ctc_grad<double>(const CtcGradArgs<double>&, const CtcPlan&, hipStream_t);
 
 }  // namespace sctc

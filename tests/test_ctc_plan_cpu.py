@@ -1,0 +1,219 @@
+"""Which CTC kernel a batch runs and how its workspace is laid out (csrc/ctc_plan.h), checked without a GPU.
+
+The header is pure host code: tests/ctc_plan_dump.cpp prints its decisions, compiled here with g++.
+  * tests/data/ctc_plan_parent.txt holds the decisions of the hand-written dispatch this header replaced (commit
+    6d568d0: ctc_make_plan / run_ctc in capi_ctc.hip, ctc_lattice_shape, launch_fused_k / launch_fused_one, the NA
+    expressions of three launchers), recorded from that code itself on the CPU: its capi_ctc.hip, ctc_fused.hip,
+    ctc_fusedw.hip, ctc_kernels.hip and ctc_generic.hip compiled host-only (hipcc --cuda-host-only) and linked against
+    a stand-in of the HIP runtime calls they make, which reports success, names every launched kernel by the demangled
+    symbol the object registered for it, reads the slice offsets out of the kernel arguments and every utterance's
+    lat_off out of the descriptor upload.  A driver called sctc_ctc_workspace_bytes and sctc_ctc_loss_batch under
+    setenv for: rows of 2U+1 states on both sides of 128 / 256 / 512 / 1024 / 2048 and U = 1, batches on both sides of
+    18 / 24 / 256 / 1025 utterances and 1, alphabets on both sides of 64 / 128 / 256, both dtypes, 33 switch settings
+    (every switch alone at the values tests and tools use, and their combinations): 39204 calls at T = 1, stored with
+    equal kernel lists written once; and three ragged batches (one with rows beyond 2048 states) under the same
+    settings, stored with every lat_off, slice offset and the total bytes.  To repeat it: check that commit out, build
+    the five sources as described, and print in the format of `ctc_plan_dump grid`.  The header's decisions must
+    equal the table line by line.
+  * every name of tests/test_gpu_ctc_paths.py's `path.ENV` reaches the kernel it names on every shape of its SHAPES,
+    and the two through-the-network minibatches take the wide kernel by default and the lattice pair with
+    SCTC_CTC_FUSED=0 -- what the GPU tests can only infer from numeric differences;
+  * moving any one threshold in a copy of the header makes the table test fail.
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import test_gpu_ctc_paths as paths
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "stanford-ctc_amd", "csrc")
+RECORDED = os.path.join(ROOT, "tests", "data", "ctc_plan_parent.txt")
+DUMP_SRC = os.path.join(ROOT, "tests", "ctc_plan_dump.cpp")
+
+GRID_U = [1, 63, 64, 127, 128, 255, 256, 511, 512, 1023, 1024]
+GRID_B = [1, 17, 18, 23, 24, 256, 257, 1024, 1025]
+GRID_A = [64, 65, 128, 129, 256, 257]
+N_SETS = 33
+
+
+def _compile(exe, include_dir, opt="-O1"):
+    subprocess.check_call(["g++", "-std=c++17", opt, "-Wall", "-Wextra", "-Werror", "-I", include_dir, DUMP_SRC, "-o", exe])
+    return exe
+
+
+@pytest.fixture(scope="module")
+def dump(tmp_path_factory):
+    return _compile(str(tmp_path_factory.mktemp("ctc_plan") / "ctc_plan_dump"), CSRC)
+
+
+def _clean_env(extra=()):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SCTC_CTC_")}
+    env.update(extra)
+    return env
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    """tests/data/ctc_plan_parent.txt expanded to what `ctc_plan_dump grid` prints"""
+    bodies, plans, tail, sets = {}, {}, [], None
+    for line in open(RECORDED).read().splitlines():
+        if line.startswith("sets: "):
+            sets = line.split()[1:]
+        elif line.startswith("P") and " = " in line and not tail:
+            name, body = line.split(" = ")
+            bodies[name[1:]] = body.split(" | ")
+        elif line.startswith("plan "):
+            head, entries = line.split(": ")
+            _, L, B, A = head.split()
+            plans[int(L), int(B), int(A)] = entries.split()
+        else:
+            tail.append(line)
+    assert len(sets) == N_SETS and sets[0] == "default"
+    assert sorted(plans) == sorted((2 * U + 1, B, A) for U in GRID_U for B in GRID_B for A in GRID_A)
+    out = []
+    for U in GRID_U:
+        for B in GRID_B:
+            for A in GRID_A:
+                refs = plans[2 * U + 1, B, A]
+                assert len(refs) == 2 * N_SETS
+                for dtype in (0, 1):
+                    for i, name in enumerate(sets):
+                        out.append("plan %d %d %d %d %s" % (2 * U + 1, B, A, dtype, name))
+                        out += [" " + k for k in bodies[refs[dtype * N_SETS + i]]]
+    assert sum(l.startswith("layout ") for l in tail) == 3 * 2 * N_SETS
+    assert sum(l.startswith(" lat_off ") for l in tail) == sum(l.startswith(" bytes ") for l in tail) == 3 * 2 * N_SETS
+    return out + tail
+
+
+def _first_difference(got, want):
+    for i, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            head = max(j for j in range(i + 1) if want[j].startswith(("plan ", "layout ")))
+            return "line %d: got %r, recorded %r (under %r)" % (i + 1, g, w, want[head])
+    return None if len(got) == len(want) else "%d lines, recorded %d" % (len(got), len(want))
+
+
+def test_decisions_equal_the_recorded_dispatch(dump, recorded):
+    got = subprocess.check_output([dump, "grid"], universal_newlines=True, env=_clean_env()).splitlines()
+    assert sum(l.startswith("plan ") for l in recorded) == 11 * 9 * 6 * 2 * N_SETS
+    assert _first_difference(got, recorded) is None, _first_difference(got, recorded)
+
+
+def kernels(dump, env, queries):
+    """queries: (B, A, dtype, max_L, max_T) -> per query the list of kernel template-ids under the switches `env`"""
+    text = "".join("%d %d %d %d %d\n" % q for q in queries)
+    out = subprocess.run([dump, "query"], input=text, stdout=subprocess.PIPE, check=True, universal_newlines=True,
+                         env=_clean_env(env)).stdout.splitlines()
+    res, cur = [], []
+    for line in out:
+        if line == "end":
+            res.append(cur)
+            cur = []
+        else:
+            cur.append(line.strip())
+    assert len(res) == len(queries)
+    return res
+
+
+def _args(name):
+    return name[name.index("<") + 1:-1].split(", ")
+
+
+def _na(A):
+    return 1 if A <= 64 else (2 if A <= 128 else 4)
+
+
+def _fused_k(L):
+    return 2 if L <= 128 else (4 if L <= 256 else 8)
+
+
+def _is_lattice_pair(got, ri):
+    return (len(got) == 2 and got[0].startswith("ctc_lattice_kernel<%s, " % ri) and _args(got[0])[4] == "false"
+            and got[1].startswith("ctc_grad_kernel<%s, " % ri))
+
+
+@pytest.mark.parametrize("name", sorted(paths.path.ENV))
+def test_every_named_path_reaches_the_kernel_it_names(dump, name):
+    """single utterances of every shape of test_gpu_ctc_paths.SHAPES, as ctc_loss (float64) and ctc_loss_batch on
+    float32 probabilities present them.  One listed shape has 513 states, one more than the narrow fused kernel holds:
+    there the "fused*" names run what the default dispatch runs for a single utterance, the lattice pair."""
+    env = paths.path.ENV[name]
+    assert set(env) <= set(paths.path.VARS)
+    queries = [(1, A, dtype, 2 * U + 1, T) for A, T, U in paths.SHAPES for dtype in (0, 1)]
+    dieted = 0
+    for (B, A, dtype, L, T), got in zip(queries, kernels(dump, env, queries)):
+        ri = "double" if dtype else "float"
+        rows = "double" if dtype or name in ("fused64", "wide64") else "unsigned int"
+        K, NA, tag = _fused_k(L), _na(A), (name, A, L, ri, got)
+        if name.startswith("fused") and L > 512:
+            assert _is_lattice_pair(got, ri), tag
+        elif name.startswith("fused") or (name == "widemin1" and L <= 512):
+            helpers_exist = (NA == 1 and rows == "unsigned int") if K == 8 else NA <= 2
+            help_ = helpers_exist and name not in ("fused2w", "fused2wd")
+            diet = name == "fused2wd" and ri == "float" and rows == "unsigned int" and K <= 4 and NA == 1
+            dieted += diet
+            assert got == ["ctc_fused_kernel<%s, %s, %d, %d, %s, %s>" % (ri, rows, K, NA, str(help_).lower(), str(diet).lower())], tag
+        elif name.startswith("wide"):
+            W = 8 if name == "wide8" else 4
+            assert got == ["ctc_fusedw_kernel<%s, %s, %d, %d, %d>" % (ri, rows, 2 if L <= 128 * W else 4, NA, W)], tag
+        elif name == "lattice":
+            assert _is_lattice_pair(got, ri), tag
+        else:
+            assert name == "generic"
+            assert got == ["ctc_lattice_generic_kernel<%s>" % ri, "ctc_grad_generic_kernel<%s>" % ri], tag
+    assert (dieted > 0) == (name == "fused2wd")
+
+
+def test_the_network_minibatches_take_the_wide_kernel_and_the_lattice_pair(dump):
+    """test_wide_rows_through_the_network (25 utterances, label rows of at most 1201 states) and
+    test_cfg5_rows_at_18_utterances_through_the_network (18 of 1601 states), float32 probabilities: "fused" = the
+    default switches is the wide kernel, "lattice" the lattice + grad pair -- so their two runs differ in kernels"""
+    rs = np.random.RandomState(12)
+    Us = [int(rs.randint(300, 601)) for _ in range(25)]
+    Ts = [int(u + rs.randint(60, 400)) for u in Us]
+    assert 1024 < 2 * max(Us) + 1 <= 1201
+    queries = [(25, 20, 0, 2 * max(Us) + 1, max(Ts)), (18, 33, 0, 1601, 8000)]
+    for got in kernels(dump, paths.path.ENV["fused"], queries):
+        assert got == ["ctc_fusedw_kernel<float, unsigned int, 4, 1, 8>"]
+    for got in kernels(dump, paths.path.ENV["lattice"], queries):
+        assert got == ["ctc_lattice_kernel<float, 4, 1, 8, false>", "ctc_grad_kernel<float, 16>"]
+    # one utterance fewer than the 18: the lattice pair by default
+    assert _is_lattice_pair(kernels(dump, {}, [(17, 33, 0, 1601, 8000)])[0], "float")
+
+
+# (text of csrc/ctc_plan.h, its replacement): each moves one threshold by one or two
+MUTATIONS = [
+    ("(s.max_L > 1024 ? 18 : 24)", "(s.max_L > 1024 ? 19 : 24)"),
+    ("(s.max_L > 1024 ? 18 : 24)", "(s.max_L > 1024 ? 18 : 25)"),
+    ("(s.max_L > 1024 ? 18 : 24)", "(s.max_L > 1026 ? 18 : 24)"),
+    ("int helper_max_b = 256;", "int helper_max_b = 255;"),
+    ("int diet_min_b = 1025;", "int diet_min_b = 1026;"),
+    ("s.max_L <= 128 ? 2 :", "s.max_L <= 130 ? 2 :"),
+    ("(s.max_L <= 256 ? 4 :", "(s.max_L <= 258 ? 4 :"),
+    ("(s.max_L <= 512 ? 8 : 0)", "(s.max_L <= 514 ? 8 : 0)"),
+    ("s.max_L > 2048 ||", "s.max_L > 2050 ||"),
+    ("p.W = (s.max_L > 1024 ||", "p.W = (s.max_L > 1026 ||"),
+    ("(force == 0 && max_L <= 256)", "(force == 0 && max_L <= 258)"),
+    ("(force == 0 && max_L > 1024)", "(force == 0 && max_L > 1026)"),
+    ("return A <= 64 ? 1 : (A <= 128 ? 2 : 4);", "return A <= 65 ? 1 : (A <= 128 ? 2 : 4);"),
+    ("return A <= 64 ? 1 : (A <= 128 ? 2 : 4);", "return A <= 64 ? 1 : (A <= 129 ? 2 : 4);"),
+    ("|| s.A > 256 ||", "|| s.A > 257 ||"),
+    ("p.NB = p.lp <= 256 ? 4 :", "p.NB = p.lp <= 128 ? 4 :"),
+    # (the layout half of the table: the pad in front of every utterance's packed rows)
+    ("return p.K + (int64_t)T *", "return (int64_t)T *"),
+]
+
+
+@pytest.mark.parametrize("i", range(len(MUTATIONS)))
+def test_a_moved_threshold_is_noticed(tmp_path, recorded, i):
+    old, new = MUTATIONS[i]
+    text = open(os.path.join(CSRC, "ctc_plan.h")).read()
+    assert text.count(old) == 1, old
+    text = text.replace(old, new).replace('"../../include/sctc.h"', '"%s"' % os.path.join(ROOT, "include", "sctc.h"))
+    (tmp_path / "ctc_plan.h").write_text(text)
+    exe = _compile(str(tmp_path / "ctc_plan_dump"), str(tmp_path), opt="-O0")
+    got = subprocess.check_output([exe, "grid"], universal_newlines=True, env=_clean_env()).splitlines()
+    assert _first_difference(got, recorded) is not None, (old, new)
