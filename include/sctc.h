@@ -177,7 +177,8 @@ int sctc_ctc_beam_decode_batch(const sctc_beam_config* cfg, const void* probs_de
 
 /* ---- decoding to words: ctc_fast/decoder/bg_decoder.pyx decode_bg_lm -----
  * Added without an ABI version bump (still 6): sctc_lexicon_create / sctc_lexicon_destroy /
- * sctc_lexicon_bytes, sctc_ctc_lexbeam_workspace_bytes, sctc_ctc_lexbeam_decode_batch. */
+ * sctc_lexicon_bytes, sctc_ctc_lexbeam_workspace_bytes, sctc_ctc_lexbeam_decode_batch;
+ * sctc_lexicon_create_ngram (§4.6b). */
 
 /* A lexicon on the device (stanford-ctc_amd/decoder/prefixTree.py flattens it): the prefix tree of
  * the word list and the word-bigram LM of fastdecode/lm.cpp.
@@ -196,14 +197,39 @@ int sctc_lexicon_create(const int32_t* child_host, const int32_t* word_host, int
                         int32_t space, const float* ug_prob_host, const float* ug_backoff_host, int64_t n_words,
                         const uint64_t* bg_keys_host, const float* bg_vals_host, int64_t bg_capacity,
                         int32_t start_word, sctc_lexicon_t* out);
+
+/* The same lexicon with a word n-gram LM of order 2..5 in place of the bigram (DESIGN.md §4.6b;
+ * stanford-ctc_amd/decoder/ngram_lm.py packs it).  The tree and the unigram arrays as above, then
+ *   ng_keys_host / ng_vals_host / ng_backoffs_host / ng_ids_host [ng_capacity]  every listed n-gram
+ *                           w1..wn of length 2..order in one open-addressing table of the same make:
+ *                           key (id of w1..w(n-1) << 32) | wn, its natural-log value, its back-off (0
+ *                           without one) and its own id, -1 at length `order`
+ *   n_contexts              the listed n-grams of length 2..order-1: their ids are n_words ..
+ *                           n_words + n_contexts - 1; the id of a unigram is its word id
+ * The prefix of every listed n-gram must be listed; its suffix need not be.  P(w | h), h the last
+ * order-1 words of <s> and the finished words, is the ARPA back-off rule with float32 partial sums: the
+ * value of the longest listed h' w, the match extended one context word at a time and stopped at the
+ * first miss, plus the back-offs of the contexts from that length up to h, shortest first, stopped at
+ * the first context that is not listed.  A listed value of exactly 0 is a value.  The handle goes to
+ * sctc_ctc_lexbeam_workspace_bytes / sctc_ctc_lexbeam_decode_batch like a bigram lexicon, whose LM term
+ * then is alpha * P(word | h).  Checked here, before anything is allocated: order 2..5, the tree as above, the
+ * capacity, every key's context id and word, and that the ids fit the n-grams -- every context id is a word or the
+ * id of exactly one listed n-gram, and an n-gram has an id exactly when it is shorter than `order`.  Values and
+ * back-offs are taken as given. */
+int sctc_lexicon_create_ngram(const int32_t* child_host, const int32_t* word_host, int64_t nodes, int32_t A,
+                              int32_t space, const float* ug_prob_host, const float* ug_backoff_host, int64_t n_words,
+                              const uint64_t* ng_keys_host, const float* ng_vals_host, const float* ng_backoffs_host,
+                              const int32_t* ng_ids_host, int64_t ng_capacity, int64_t n_contexts, int32_t order,
+                              int32_t start_word, sctc_lexicon_t* out);
 int sctc_lexicon_destroy(sctc_lexicon_t lexicon);
 /* bytes of device memory the lexicon holds (0 for NULL) */
 size_t sctc_lexicon_bytes(sctc_lexicon_t lexicon);
 
 /* decode_bg_lm(probs, prefixTree, lm, beam, alpha, beta) for B utterances: the prefix beam search of
  * sctc_ctc_beam_decode_batch in which a prefix may only spell lexicon words separated by `space`, the
- * LM term is alpha * bg_prob(previous word, word) when the space after a word is emitted, and the sort
- * key is log(p_nb + p_b) + beta * (words finished). */
+ * LM term is alpha * bg_prob(previous word, word) when the space after a word is emitted (alpha * P(word |
+ * the last order-1 words) for a lexicon of sctc_lexicon_create_ngram), and the sort key is
+ * log(p_nb + p_b) + beta * (words finished). */
 typedef struct sctc_lexbeam_config {
     int32_t B;                 /* utterances */
     int32_t A;                 /* symbols incl. blank: the A the lexicon was created with */

@@ -120,6 +120,9 @@ PROTOTYPES = {
     "sctc_lexicon_create": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, vp,
                                            ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.POINTER(vp)]),
+    "sctc_lexicon_create_ngram": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, vp,
+                                                 ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]),
     "sctc_lexicon_destroy": (ctypes.c_int, [vp]),
     "sctc_lexicon_bytes": (ctypes.c_size_t, [vp]),
     "sctc_ctc_lexbeam_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(LexBeamConfig)]),

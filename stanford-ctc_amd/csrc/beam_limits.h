@@ -8,7 +8,8 @@ namespace beam {
 
 constexpr int AMAX = 256;               // alphabet limit
 constexpr int KMAX = 256;               // beam limit
-constexpr uint64_t BG_EMPTY = ~0ull;    // an empty slot of the lexicon's bigram table
+constexpr uint64_t BG_EMPTY = ~0ull;    // an empty slot of the lexicon's bigram or n-gram table
+constexpr int NG_MAX_ORDER = 5;         // highest order of the lexicon's word n-gram LM
 
 }  // namespace beam
 }  // namespace sctc

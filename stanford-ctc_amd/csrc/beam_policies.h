@@ -2,6 +2,7 @@
 // n-gram LM, or none, is written out in beam_ngram.h:
 //   LexiconPolicy  a prefix tree of words with a word-bigram LM (the reference's
 //                  ctc_fast/decoder/bg_decoder.pyx:18-95) -- §4.6
+//   LexiconNgramPolicy  the same tree with a word n-gram LM of order 2..5 -- §4.6b
 //   NNPolicy       a window neural LM supplies the rows (the lexicon-free path of the reference's
 //                  ctc_fast/decoder/clm_decoder2.pyx), through nnlm_tile, the routine sctc_nnlm_rows runs -- §4.7
 //   RNNPolicy      a recurrent neural LM supplies them (the `rnn` model type of clm_decoder2.pyx), through
@@ -155,6 +156,157 @@ struct LexiconPolicy {
         NX.nw[r] = X.nw[j] + sp;
         NX.wd[r] = wd;
         NX.bg[r] = wd >= 0 ? lex_bg(a, pw, wd) : 0.0f;
+    }
+    __device__ __forceinline__ void new_rows(const BeamArgs&, const Beam&, int, int, const FrameScratch&) {}
+};
+
+// ---- lexicon with a word n-gram LM of order 2..5 (§4.6b) --------------------------------------------
+
+struct LexiconNgramArgs {
+    const int32_t* child;
+    const int32_t* word;
+    const float* ug;
+    const float* bo;
+    const uint64_t* key;   // (context id << 32) | w of every listed n-gram of length >= 2, all ones = empty
+    const float* val;
+    const float* nbo;      // the n-gram's own back-off
+    const int32_t* id;     // the n-gram's id as a context, -1 at full order
+    uint64_t mask;
+    int32_t start, space, order;
+};
+
+constexpr int NG_HIST = NG_MAX_ORDER - 1;   // history ids of the highest order
+
+// per beam entry; a function of the prefix alone.  The history is the last min(order - 1, finished words + 1)
+// word ids of <s> + the finished words, newest first, -1 beyond its length.
+struct LexNgState {
+    int32_t node[KMAX];   // prefix-tree node the unfinished word has reached (0 = root)
+    int32_t nw[KMAX];     // finished words
+    int32_t wd[KMAX];     // word id of `node`, -1: a space cannot follow
+    float lm[KMAX];       // P(wd | history): the LM value of the space extension, 0 without one
+    int32_t h0[KMAX], h1[KMAX], h2[KMAX], h3[KMAX];
+};
+
+// slot of the listed n-gram (context, w), -1 for none; ends at the table's empty slot
+__device__ inline int64_t ng_find(const LexiconNgramArgs& a, int ctx, int w)
+{
+    const uint64_t key = ((uint64_t)(uint32_t)ctx << 32) | (uint32_t)w;
+    uint64_t s = mix64(key) & a.mask;
+    while (true) {
+        const uint64_t k = a.key[s];
+        if (k == key) return (int64_t)s;
+        if (k == BG_EMPTY) return -1;
+        s = (s + 1) & a.mask;
+    }
+}
+
+// P(w | h) by the ARPA back-off rule in kenlm's order of float32 additions (arpa_lm.ArpaLM.score_ids; the
+// host twin is decoder/ngram_lm.py walk_packed).  Per context length m: the id of the history's suffix of
+// that length by chaining from its oldest word -- a miss means the suffix is not listed, and then neither
+// is any n-gram it begins (the loader requires every listed n-gram's prefix) -- then (suffix, w) while the
+// match holds, and the suffix's back-off from the first miss on.  Both stop at the first suffix that is not
+// listed.  h is indexed by constants only, so it stays in registers.
+__device__ __forceinline__ float lex_ng(const LexiconNgramArgs& a, const int32_t (&h)[NG_HIST], int w)
+{
+    float p = a.ug[w];
+    bool matching = true, open = true;
+#pragma unroll
+    for (int m = 1; m <= NG_HIST; ++m) {
+        open = open && h[m - 1] >= 0;
+        int cid = open ? h[m - 1] : 0;
+        float cbo = m == 1 ? a.bo[cid] : 0.0f;
+#pragma unroll
+        for (int i = m - 2; i >= 0; --i) {
+            if (open) {
+                const int64_t s = ng_find(a, cid, h[i]);
+                if (s < 0) {
+                    open = false;
+                } else {
+                    cid = a.id[s];
+                    cbo = a.nbo[s];
+                }
+            }
+        }
+        if (open) {
+            int64_t s = -1;
+            if (matching) s = ng_find(a, cid, w);
+            if (s >= 0) {
+                p = a.val[s];
+            } else {
+                matching = false;
+                p += cbo;
+            }
+        }
+    }
+    return p;
+}
+
+// LexiconPolicy with the history of an n-gram in place of the previous word
+struct LexiconNgramPolicy {
+    using Args = LexiconNgramArgs;
+    using State = LexNgState;
+    const Args& a;
+
+    __device__ __forceinline__ LexiconNgramPolicy(const BeamArgs&, const Args& args) : a(args) {}
+    __device__ __forceinline__ char* carve(char* w, const BeamArgs&) { return w; }
+    __device__ __forceinline__ void empty_entry(const BeamArgs&, Beam&, State& x0)
+    {
+        x0.node[0] = 0;
+        x0.nw[0] = 0;
+        x0.wd[0] = a.word[0];
+        x0.lm[0] = 0.0f;
+        x0.h0[0] = a.start;
+        x0.h1[0] = -1;
+        x0.h2[0] = -1;
+        x0.h3[0] = -1;
+    }
+    __device__ __forceinline__ void empty_rows(const BeamArgs&, const Beam&) {}
+    __device__ __forceinline__ bool candidate(const BeamArgs& p, const State& X, int j, int c) const
+    {
+        return c == a.space ? X.wd[j] >= 0 : a.child[(int64_t)X.node[j] * p.A + c] >= 0;
+    }
+    __device__ __forceinline__ double lm_term(const BeamArgs& p, const State& X, int e, int c) const
+    {
+        return c == a.space ? p.alpha * (double)X.lm[e] : 0.0;
+    }
+    __device__ __forceinline__ int counted_len(const BeamArgs&, const Beam&, const State& X, int j, int c) const
+    {
+        return c == 0 ? X.nw[j] : X.nw[j] + (c == a.space);
+    }
+    __device__ __forceinline__ void carry(const BeamArgs&, const Beam&, Beam&, const State& X, State& NX, int j, int r)
+    {
+        NX.node[r] = X.node[j];
+        NX.nw[r] = X.nw[j];
+        NX.wd[r] = X.wd[j];
+        NX.lm[r] = X.lm[j];
+        NX.h0[r] = X.h0[j];
+        NX.h1[r] = X.h1[j];
+        NX.h2[r] = X.h2[j];
+        NX.h3[r] = X.h3[j];
+    }
+    // a space appends the finished word to the history and drops what is older than order - 1 words
+    __device__ __forceinline__ void extend(const BeamArgs& p, const Beam&, Beam&, const State& X, State& NX, int j, int c,
+                                           int r)
+    {
+        const bool sp = c == a.space;
+        const int nd = sp ? 0 : a.child[(int64_t)X.node[j] * p.A + c];
+        const int wd = a.word[nd];
+        int32_t h[NG_HIST] = {X.h0[j], X.h1[j], X.h2[j], X.h3[j]};
+        static_assert(NG_HIST == 4, "the history is four named arrays");
+        if (sp) {
+            h[3] = a.order > 4 ? h[2] : -1;
+            h[2] = a.order > 3 ? h[1] : -1;
+            h[1] = a.order > 2 ? h[0] : -1;
+            h[0] = X.wd[j];
+        }
+        NX.node[r] = nd;
+        NX.nw[r] = X.nw[j] + sp;
+        NX.wd[r] = wd;
+        NX.h0[r] = h[0];
+        NX.h1[r] = h[1];
+        NX.h2[r] = h[2];
+        NX.h3[r] = h[3];
+        NX.lm[r] = wd >= 0 ? lex_ng(a, h, wd) : 0.0f;
     }
     __device__ __forceinline__ void new_rows(const BeamArgs&, const Beam&, int, int, const FrameScratch&) {}
 };

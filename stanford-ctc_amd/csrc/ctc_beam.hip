@@ -1,4 +1,4 @@
-// CTC prefix beam search on the device, the four of them (DESIGN.md §4.5, §4.6, §4.7, §4.10): the n-gram
+// CTC prefix beam search on the device, the four of them (DESIGN.md §4.5, §4.6 and §4.6b, §4.7, §4.10): the n-gram
 // search (beam_ngram.h), one search body (beam_search.h) instantiated with one LM policy (beam_policies.h)
 // for each of the other three, and the host
 // side of the four -- one plan of the workspace, one launch path, and per entry point only its own
@@ -19,6 +19,11 @@ using namespace beam;
 __global__ __launch_bounds__(NT) void ctc_beam_kernel(NgramBeamArgs p) { ngram_beam_search(p); }
 
 __global__ __launch_bounds__(NT) void ctc_lexbeam_kernel(BeamArgs p, LexiconArgs lx) { beam_search<LexiconPolicy>(p, lx); }
+
+__global__ __launch_bounds__(NT) void ctc_lexngbeam_kernel(BeamArgs p, LexiconNgramArgs lx)
+{
+    beam_search<LexiconNgramPolicy>(p, lx);
+}
 
 __global__ __launch_bounds__(NT) void ctc_nnbeam_kernel(BeamArgs p, NNArgs nn) { beam_search<NNPolicy>(p, nn); }
 
@@ -260,6 +265,25 @@ int sctc_ctc_lexbeam_decode_batch(const sctc_lexbeam_config* cfg, const void* pr
     BeamPlan pl;
     SCTC_TRY(plan_lexicon(cfg, pl));
     const sctc_lexicon* h = cfg->lexicon;
+    const BeamIO io{probs_dev, ids_dev, lengths_dev, scores_dev, workspace_dev, workspace_bytes, stream};
+    if (h->order) {   // a word n-gram LM: the kernel of its policy (§4.6b)
+        LexiconNgramArgs ng{};
+        ng.child = h->child;
+        ng.word = h->word;
+        ng.ug = h->ug;
+        ng.bo = h->bo;
+        ng.key = h->bg_key;
+        ng.val = h->bg_val;
+        ng.nbo = h->ng_bo;
+        ng.id = h->ng_id;
+        ng.mask = (uint64_t)(h->bg_cap - 1);
+        ng.start = h->start;
+        ng.space = cfg->space;
+        ng.order = h->order;
+        return launch_beam("lexbeam", view_of(*cfg), pl, io, nullptr, false, -1, [&](hipStream_t s, const BeamArgs& a) {
+            hipLaunchKernelGGL(ctc_lexngbeam_kernel, dim3(cfg->B), dim3(NT), 0, s, a, ng);
+        });
+    }
     LexiconArgs lx{};
     lx.child = h->child;
     lx.word = h->word;
@@ -270,8 +294,7 @@ int sctc_ctc_lexbeam_decode_batch(const sctc_lexbeam_config* cfg, const void* pr
     lx.mask = (uint64_t)(h->bg_cap - 1);
     lx.start = h->start;
     lx.space = cfg->space;
-    return launch_beam("lexbeam", view_of(*cfg), pl,
-                       BeamIO{probs_dev, ids_dev, lengths_dev, scores_dev, workspace_dev, workspace_bytes, stream},
+    return launch_beam("lexbeam", view_of(*cfg), pl, io,
                        nullptr, false, -1, [&](hipStream_t s, const BeamArgs& a) {
                            hipLaunchKernelGGL(ctc_lexbeam_kernel, dim3(cfg->B), dim3(NT), 0, s, a, lx);
                        });

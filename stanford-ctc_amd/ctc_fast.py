@@ -506,51 +506,76 @@ class DecodeLexicon(_DeviceHandle):
     ``words`` (plus ``specials``, tokens that are whole words) and the word-bigram LM ``arpa``
     (a :class:`decoder.lm.LM` or the path of an ARPA file), flattened and uploaded once.
 
+    order: 2 (the default) with a path or an ``LM`` is the word-bigram LM of DESIGN.md §4.6; 3..5 with
+    a path reads the file as a :class:`decoder.ngram_lm.NgramLM` of that order (§4.6b), and an
+    ``NgramLM`` given as ``arpa`` is used at its own order, 2 included: with one, ``order`` is left at
+    its default or names the LM's own order, anything else is a ``ValueError``.
+
     chars: {token: symbol id} or the path of a ``token id`` file; words: a list or the path of a
     word list; space: the separator token or its symbol id; A: the alphabet size of the inputs
     (default: the largest symbol id + 1)."""
 
     _destroy = "sctc_lexicon_destroy"
 
-    def __init__(self, words, chars, arpa, space, specials=(), A=None):
-        from decoder import decoder_utils, lm as lm_mod, prefixTree
+    def __init__(self, words, chars, arpa, space, specials=(), A=None, order=2):
+        from decoder import decoder_utils, lm as lm_mod, ngram_lm, prefixTree
+        order = int(order)
+        if not ngram_lm.MIN_ORDER <= order <= ngram_lm.MAX_ORDER:
+            raise ValueError("DecodeLexicon: order %d outside %d..%d" % (order, ngram_lm.MIN_ORDER, ngram_lm.MAX_ORDER))
+        if isinstance(arpa, lm_mod.LM) and order != 2:
+            raise ValueError("DecodeLexicon: a decoder.lm.LM holds bigrams only; order %d needs a path or an NgramLM"
+                             % order)
+        if isinstance(arpa, ngram_lm.NgramLM) and order not in (2, arpa.order):
+            raise ValueError("DecodeLexicon: order %d asked, the NgramLM was read at order %d" % (order, arpa.order))
         if isinstance(chars, str):
             chars = decoder_utils.load_chars(chars)
         if isinstance(words, str):
             words = decoder_utils.load_words(words)
-        if not isinstance(arpa, lm_mod.LM):
-            arpa = lm_mod.LM(arpa)
+        if not isinstance(arpa, (lm_mod.LM, ngram_lm.NgramLM)):
+            arpa = lm_mod.LM(arpa) if order == 2 else ngram_lm.NgramLM(arpa, order)
         tree = prefixTree.PrefixTree(chars, words, arpa, specials=specials, space=space)
         self.handle = None
         self._upload(tree, arpa, int(A) if A is not None else max(chars.values()) + 1)
 
     @classmethod
     def from_tree(cls, tree, lm, A):
-        """from a built :class:`decoder.prefixTree.PrefixTree` and its LM"""
+        """from a built :class:`decoder.prefixTree.PrefixTree` and its LM, a :class:`decoder.lm.LM` or a
+        :class:`decoder.ngram_lm.NgramLM`"""
         self = cls.__new__(cls)
         self.handle = None
         self._upload(tree, lm, int(A))
         return self
 
     def _upload(self, tree, lm, A):
+        from decoder import ngram_lm
         self.tree, self.lm, self.A, self.space = tree, lm, A, int(tree.space)
         child, word = tree.flatten(A)
-        keys, vals = lm.pack_bigrams()
+        self.order = lm.order if isinstance(lm, ngram_lm.NgramLM) else 2
+        table = lm.pack() if isinstance(lm, ngram_lm.NgramLM) else lm.pack_bigrams()
         self.nodes = child.shape[0]
         _sctc.require_gpu()
         h = ctypes.c_void_p()
         ug = np.ascontiguousarray(lm.ug, dtype=np.float32)
         bo = np.ascontiguousarray(lm.bo, dtype=np.float32)
-        rc = _sctc.lib().sctc_lexicon_create(child.ctypes.data, word.ctypes.data, child.shape[0], A, self.space,
-                                             ug.ctypes.data, bo.ctypes.data, ug.shape[0], keys.ctypes.data,
-                                             vals.ctypes.data, keys.shape[0], int(lm.start), ctypes.byref(h))
+        tree_args = (child.ctypes.data, word.ctypes.data, child.shape[0], A, self.space, ug.ctypes.data,
+                     bo.ctypes.data, ug.shape[0])
+        if isinstance(lm, ngram_lm.NgramLM):
+            keys, vals, bos, ids, contexts = table
+            rc = _sctc.lib().sctc_lexicon_create_ngram(*(tree_args + (keys.ctypes.data, vals.ctypes.data, bos.ctypes.data,
+                                                                      ids.ctypes.data, keys.shape[0], contexts,
+                                                                      lm.order, int(lm.start), ctypes.byref(h))))
+        else:
+            keys, vals = table
+            rc = _sctc.lib().sctc_lexicon_create(*(tree_args + (keys.ctypes.data, vals.ctypes.data, keys.shape[0],
+                                                                int(lm.start), ctypes.byref(h))))
         _sctc.check(rc, "DecodeLexicon")
         self.handle = h
         self.device_bytes = int(_sctc.lib().sctc_lexicon_bytes(h))
 
 
 def decode_lexicon_beam_batch(logprobs, lengths=None, lexicon=None, beam=40, alpha=1.0, beta=0.0, nbest=1):
-    """Lexicon-constrained CTC prefix beam search with a word-bigram LM, batched (DESIGN.md
+    """Lexicon-constrained CTC prefix beam search with a word-bigram LM, or with a word n-gram LM of
+    order 2..5 when the lexicon was built with one (§4.6b), batched (DESIGN.md
     §4.6): the reference's ``decode_bg_lm`` (ctc_fast/decoder/bg_decoder.pyx:18-95) for every
     utterance at once, one workgroup per utterance.  Inputs and outputs as
     :func:`decode_beam_batch`; lexicon: a :class:`DecodeLexicon`.  A hypothesis spells lexicon

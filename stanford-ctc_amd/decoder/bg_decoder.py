@@ -5,7 +5,9 @@
 ``probs`` is a float64 (A, T) Fortran-ordered array of natural-log probabilities, as the
 ``double[::1,:] probs not None`` signature accepts; anything else raises like the memoryview
 does.  The search runs on the GPU (csrc/ctc_beam.hip); the tree and the LM are
-uploaded once per (tree, alphabet size) and kept on the tree object.  ``decode_bg_lm_batch``
+uploaded once per (tree, alphabet size) and kept on the tree object.  ``lm`` is a ``decoder.lm.LM``
+(the reference's word bigram) or a ``decoder.ngram_lm.NgramLM`` of order 2..5 (§4.6b), for which the
+LM term of a finished word is ``alpha * P(word | the last order-1 words)``.  ``decode_bg_lm_batch``
 (not in the reference) decodes a list of utterances in one launch."""
 import numpy as np
 

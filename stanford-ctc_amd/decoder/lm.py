@@ -8,7 +8,8 @@ file: ``LM(arpafile)`` with ``start``, ``end``, ``unk``, ``get_word_id``, ``ug_p
 * ``bg_prob(w1, w2)`` is the listed bigram value when that is non-zero, otherwise the float32
   sum ``backoff(w1) + unigram(w2)`` (lm.cpp:119-127).  A listed bigram of exactly 0.0 therefore
   counts as missing; the quirk is kept;
-* sections of order 3 and above are ignored;
+* sections of order 3 and above are ignored by this class: ``decoder.ngram_lm.NgramLM`` reads them
+  (orders 2..5, DESIGN.md §4.6b);
 * an unknown word has the id of ``<UNK>`` (``<unk>`` is accepted too); without either it is a
   ``ValueError`` where the C++ would silently use id 0.
 """

@@ -15,6 +15,7 @@ next to the character error rate (reference words: the alignment split at the sp
 
     python runDecode.py --method bg --likelihoods loglikelihoods_1.pk --chars chars.txt --alis alis1.txt \\
         --words wordlist --word-lm text_word.2g.arpa --out hyps.txt [--specials [noise] [laughter]]
+        [--word-lm-order 3]
 
 ``--errors FILE`` writes ``key dist ins dels subs corr`` for every scored utterance (characters
 against the alignment, the naming of editDistance.py) and adds a line of totals to the summary;
@@ -184,10 +185,11 @@ def tokens(hyp, char_int_map):
 
 
 def decode_bg(a, ll):
-    """--method bg: (CER, WER) of the lexicon-constrained word-bigram search"""
+    """--method bg: (CER, WER) of the lexicon-constrained search with a word bigram, or a word n-gram of
+    --word-lm-order"""
     chars = decoder_utils.load_chars(a.chars)
     alis = load_alis(a.alis, a.chars)
-    lex = ctc_fast.DecodeLexicon(a.words, chars, a.word_lm, a.space, specials=a.specials)
+    lex = ctc_fast.DecodeLexicon(a.words, chars, a.word_lm, a.space, specials=a.specials, order=a.word_lm_order)
     keys = sorted(ll)
     errs = n_ref = werrs = n_words = 0
     with open(a.out, "w") as out, ErrorLog(a.errors) as log:
@@ -229,7 +231,10 @@ def main(argv=None):
     ap.add_argument("--method", choices=("char", "bg"), default="char",
                     help="char: character LM (default); bg: word list and word-bigram LM")
     ap.add_argument("--words", help="word list, one per line (--method bg)")
-    ap.add_argument("--word-lm", help="ARPA word-bigram LM (--method bg)")
+    ap.add_argument("--word-lm", help="ARPA word LM (--method bg)")
+    ap.add_argument("--word-lm-order", type=int, default=2,
+                    help="order 2..5 at which --word-lm is read: 2 is the reference's word bigram, 3..5 use the "
+                         "file's higher sections too (default 2)")
     ap.add_argument("--specials", nargs="*", default=[], help="tokens of chars.txt that are whole words")
     ap.add_argument("--space", default="[space]", help="the word separator token of chars.txt")
     ap.add_argument("--out", required=True)

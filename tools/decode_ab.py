@@ -1,15 +1,17 @@
-"""Bit equality of the four prefix beam searches between two builds of the library (DESIGN.md §4.5,
-§4.6, §4.7, §4.10).  One run decodes seeded inputs through ctc_fast with the library SCTC_LIB_PATH
+"""Bit equality of the prefix beam searches between two builds of the library (DESIGN.md §4.5,
+§4.6, §4.6b, §4.7, §4.10).  One run decodes seeded inputs through ctc_fast with the library SCTC_LIB_PATH
 names (default: the tree's own) and writes every result to an .npz; --compare requires two such files
-to hold the same arrays, byte for byte.
+to hold the same arrays, byte for byte.  A search that only one of the files has is a difference,
+unless --allow-missing names it (a build older than the search cannot have it): then it is named and
+not compared.
 
     SCTC_LIB_PATH=/path/to/parent/libsctc_hip.so python tools/decode_ab.py parent.npz
     python tools/decode_ab.py new.npz
-    python tools/decode_ab.py --compare parent.npz new.npz
+    python tools/decode_ab.py --compare parent.npz new.npz [--allow-missing lexng]
 
 Each run is a process of its own: a process loads one library.  The inputs are small and reach every
 path: A = 35 with the LM fixtures of tests/golden (lm_char_5g.arpa, words_bg.txt + lm_word_2g.arpa,
-lm_char_nn.npz, lm_char_rnn.npz), the character search also without an LM, beams 1, 24 and 150, nbest 1
+the same lexicon with lm_word_4g.arpa at order 4, lm_char_nn.npz, lm_char_rnn.npz), the character search also without an LM, beams 1, 24 and 150, nbest 1
 and 3, a batch of T = 0, 1, 7, 61 and 220 frames, float32 and float64 input, alpha 0 and 0.8.  Per case
 the file holds the ids, lengths and scores of every hypothesis and the workspace bytes the entry point
 asks for.
@@ -58,6 +60,9 @@ def providers():
     lex = ctc_fast.DecodeLexicon(words, {k: v for k, v in chars.items() if v < A},
                                  lm_mod.LM(os.path.join(GOLDEN, "lm_word_2g.arpa")), "[space]",
                                  specials=["[laughter]", "[noise]", "[vocalized-noise]"], A=A)
+    lexng = ctc_fast.DecodeLexicon(words, {k: v for k, v in chars.items() if v < A},
+                                   os.path.join(GOLDEN, "lm_word_4g.arpa"), "[space]",
+                                   specials=["[laughter]", "[noise]", "[vocalized-noise]"], A=A, order=4)
 
     def with_map(config, name):
         def nbytes(lm, head, tail):
@@ -81,6 +86,7 @@ def providers():
         "nolm": (None, chars_decode, ngram),
         "5g": (ctc_fast.DecodeLM(os.path.join(GOLDEN, "lm_char_5g.arpa"), int_char, A), chars_decode, ngram),
         "lex": (lex, lex_decode, lex_bytes),
+        "lexng": (lexng, lex_decode, lex_bytes),
         "nn": (ctc_fast.DecodeNNLM(os.path.join(GOLDEN, "lm_char_nn.npz"), int_char, A), chars_decode,
                with_map(_sctc.NNBeamConfig, "nnbeam")),
         "rnn": (ctc_fast.DecodeRNNLM(os.path.join(GOLDEN, "lm_char_rnn.npz"), int_char, A), chars_decode,
@@ -104,7 +110,7 @@ def run(path):
                     continue
                 for dt in (np.float32, np.float64):
                     for alpha in (0.0, 0.8):
-                        utts = [u.astype(dt) for u in inputs[search == "lex"]]
+                        utts = [u.astype(dt) for u in inputs[search.startswith("lex")]]
                         hyps, scores = decode(lm, utts, beam=beam, alpha=alpha, beta=BETA, nbest=nbest)
                         flat = [h for hs in hyps for h in (hs if nbest > 1 else [hs])]
                         key = "%s/beam%d/nbest%d/%s/alpha%g" % (search, beam, nbest, np.dtype(dt).name, alpha)
@@ -120,25 +126,33 @@ def run(path):
           % (len(out) // 4, _sctc.LIB_PATH, path, longest))
 
 
-def compare(pa, pb):
+def compare(pa, pb, allow_missing=()):
     a, b = np.load(pa), np.load(pb)
-    bad = sorted(set(a.files) ^ set(b.files))
-    for k in sorted(set(a.files) & set(b.files)):
+    searches = [set(k.split("/")[0] for k in z.files) for z in (a, b)]
+    for path, mine, theirs in ((pa, searches[0], searches[1]), (pb, searches[1], searches[0])):
+        for name in sorted((mine - theirs) & set(allow_missing)):
+            print("decode_ab: only %s has the search %s: not compared" % (path, name))
+    common = (searches[0] | searches[1]) - ((searches[0] ^ searches[1]) & set(allow_missing))
+    files = [set(k for k in z.files if k.split("/")[0] in common) for z in (a, b)]
+    bad = sorted(files[0] ^ files[1])
+    for k in sorted(files[0] & files[1]):
         if a[k].dtype != b[k].dtype or a[k].shape != b[k].shape or a[k].tobytes() != b[k].tobytes():
             bad.append(k)
     for k in bad[:20]:
         print("decode_ab: differs: %s" % k)
-    print("decode_ab: %d arrays compared, %d differ" % (len(a.files), len(bad)))
-    return 1 if bad or not a.files else 0
+    print("decode_ab: %d arrays of %d searches compared, %d differ" % (len(files[0] | files[1]), len(common), len(bad)))
+    return 1 if bad or not common else 0
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out", nargs="?", help="the .npz to write")
     ap.add_argument("--compare", nargs=2, metavar=("A.npz", "B.npz"))
+    ap.add_argument("--allow-missing", nargs="*", default=[], metavar="SEARCH",
+                    help="with --compare: searches that one of the two files may lack")
     a = ap.parse_args()
     if a.compare:
-        sys.exit(compare(*a.compare))
+        sys.exit(compare(*a.compare, allow_missing=a.allow_missing))
     if not a.out:
         ap.error("name the .npz to write, or --compare two")
     run(a.out)
