@@ -265,23 +265,9 @@ static size_t carve(const sctc_brnn_config* c, const Dims& d, sctc_brnn* h, void
         ctc_bytes = ctc_layout_slices(CTC_GENERIC, Bm, d.A, F, F * CTC_LP_MAX, CTC_LP_MAX, 8).bytes;
         ctc_ws = ar.take<char>(ctc_bytes);
     }
-    // split-K partials: worst case over the weight-gradient GEMMs
-    int64_t sk = 0;
-    if (c->train) {
-        for (int l = 0; l <= d.NL; ++l) {
-            const int inp = l == 0 ? d.Dp : d.Hp, outp = l == d.NL ? d.Ap : d.Hp;
-            int sp = 1;
-            sk = std::max<int64_t>(sk, gemm_plan_splits(outp, inp, (int)F, &sp, bwd_prec(c->operand_dtype), c->operand_dtype == SCTC_F16));
-        }
-        if (d.TL > 0) {
-            int sp = 1;
-            sk = std::max<int64_t>(sk, gemm_plan_splits(d.Hp, d.Hp, (int)F, &sp, bwd_prec(c->operand_dtype), c->operand_dtype == SCTC_F16));
-        }
-    }
-    // small minibatches (few row tiles) split K in the forward / delta-propagation GEMMs as well:
-    // blocks x splits stays below ~2 rounds of resident blocks, i.e. <= 2*1024 tiles of 128x128
-    sk = std::max<int64_t>(sk, std::min<int64_t>((int64_t)2 * 1024 * 128 * 128,
-                                                 (int64_t)64 * F * (std::max(d.Hp, d.Ap) + 1)));
+    // split-K partials (gemm_plan.h)
+    const int64_t sk = brnn_splitk_floats(d.Dp, d.Hp, d.Ap, d.NL, d.TL > 0, F, c->train != 0, bwd_prec(c->operand_dtype),
+                                          c->operand_dtype == SCTC_F16, gemm_switches_from_env());
     float* splitk_ws = sk ? f(sk) : nullptr;
     float* xbuf = d.TL > 0 ? f((int64_t)recurrent_xbuf_floats(d.Hp, recurrent_xrows_bound(F, F))) : nullptr;
     unsigned* counters = ar.take<unsigned>(REC_COUNTER_WORDS);
@@ -437,29 +423,74 @@ struct PhaseTimer {
     }
 };
 
-static GemmArgs gemm_defaults()
+// C [M][N] = A . B over K with operands of precision `prec` and no epilogue.  An operand is K-contiguous ([rows][K]) or
+// row-contiguous ([K][rows]), `ld` its leading dimension.
+struct GemmOperand { const float* p; int64_t ld; int kcontig; };
+static GemmArgs gemm_args(GemmOperand A, GemmOperand B, int64_t M, int64_t N, int64_t K, float* C, int64_t ldc, int prec)
 {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
+    g.A = A.p; g.lda = A.ld; g.a_kcontig = A.kcontig;
+    g.B = B.p; g.ldb = B.ld; g.b_kcontig = B.kcontig;
+    g.M = (int)M; g.N = (int)N; g.K = (int)K;
+    g.C = C; g.ldc = ldc;
+    g.prec = prec;
     g.splits = 1;
-    g.add_scale = 0.f;
     return g;
 }
 
-// deterministic split-K when the output has too few tiles to fill the machine (small minibatch)
-static void maybe_split(const sctc_brnn* h, GemmArgs& g)
+// Plans the call on its full arguments (gemm_plan.h) and launches it: split-K -- deterministic, two passes -- where the
+// plan asks for it and its partials fit the workspace carve sized, unsplit otherwise.  Every GEMM of a step goes through here.
+static int launch_gemm(const sctc_brnn* h, GemmArgs& g, hipStream_t s)
 {
-    int sp = 1;
-    const int64_t need = gemm_plan_splits(g.M, g.N, g.K, &sp, g.prec, g.in16);
-    if (sp > 1 && h->splitk_ws && need <= h->splitk_floats) {
-        g.splits = sp;
+    const GemmPlan p = gemm_plan(g);
+    if (p.splits > 1 && h->splitk_ws && p.ws_floats <= h->splitk_floats) {
+        g.splits = p.splits;
         g.splitk_ws = h->splitk_ws;
     }
+    return launch_gemm_f32(g, s);
 }
 
 static const float* tensor_ptr(const sctc_brnn* h, const float* base, int idx)
 {
     return base + h->tinfo[idx].offset;
+}
+
+// The arguments of the temporal layer's recurrence (brnnet.py:143-152) or, bptt, of its transpose run backwards in time
+// over `pre` (:212-222)
+static RecArgs rec_args(const sctc_brnn* h, bool bptt, float* pre)
+{
+    RecArgs r;
+    memset(&r, 0, sizeof(r));
+    r.W[0] = tensor_ptr(h, h->params, wf_index(h));
+    r.W[1] = tensor_ptr(h, h->params, wb_index(h));
+    r.ldw = LD(h->Hp);
+    r.transpose = bptt;
+    r.descending[0] = bptt;    // hActsFor runs from 0 up, deltasFor from T-1 down (brnnet.py:217-218)
+    r.descending[1] = !bptt;   // hActsBack runs from T-1 down, deltasBack from 0 up (brnnet.py:219-220)
+    r.pre[0] = r.pre[1] = pre;
+    r.act[0] = bptt ? h->hF : nullptr;
+    r.act[1] = bptt ? h->hB : nullptr;
+    r.out[0] = bptt ? h->dF : h->hF;
+    r.out[1] = bptt ? h->dBk : h->hB;
+    r.ld = LD(h->Hp);
+    r.Hp = h->Hp;
+    r.B = h->B;
+    r.Tmax = h->Tmax;
+    r.rowbase = h->d_rowbase;
+    r.T_b = h->d_Ts;
+    r.max_act = h->cfg.max_act;
+    r.xbuf = h->xbuf;
+    r.xbase = h->d_xbase;
+    r.n_xrows = (int)h->n_xrows;
+    r.counters = h->counters;
+    r.sync_mode = h->rec_sync_mode;
+    r.variant = h->rec_force_fallback ? REC_V_FALLBACK : h->rec_variant;
+    r.poll_delay = h->rec_poll_delay;
+    r.debug = h->rec_debug_on ? h->rec_debug + (bptt ? REC_DEBUG_WORDS : 0) : nullptr;
+    r.prec16 = h->cfg.operand_dtype == SCTC_F16;
+    r.T_host = h->Ts.data();
+    return r;
 }
 
 // ------------------------------------------------------------------ forward
@@ -485,22 +516,12 @@ static int run_forward(sctc_brnn* h, const sctc_minibatch* mb, hipStream_t s, Ph
         const sctc_tensor_info& wi = h->tinfo[weight_index(h, l)];
         const int inp = l == 0 ? h->Dp : h->Hp;
         const int outp = i == h->NL + 1 ? h->Ap : h->Hp;
-        GemmArgs g = gemm_defaults();
-        g.A = h->act[i - 1];           // [N][inp]
-        g.lda = LD(inp);
-        g.a_kcontig = 1;
-        g.B = h->params + wi.offset;   // W [outp][inp]: B(k,n) = W[n][k]
-        g.ldb = LD(inp);
-        g.b_kcontig = 1;
-        g.M = (int)N;
-        g.N = outp;
-        g.K = inp;
-        g.bias = tensor_ptr(h, h->params, bias_index(h, l));   // add_col_vec, brnnet.py:141
         float* dst = i == h->NL + 1 ? h->logits : (i == h->TL ? h->Z : h->act[i]);
-        g.C = dst;
-        g.ldc = LD(outp);
+        // brnnet.py:140: A = hActs[i-1] [N][inp]; W [outp][inp]: B(k,n) = W[n][k].  SCTC_F16 -> forward: float16 operands
+        GemmArgs g = gemm_args({h->act[i - 1], LD(inp), 1}, {h->params + wi.offset, LD(inp), 1}, N, outp, inp, dst, LD(outp),
+                               fwd_prec(h->cfg.operand_dtype));
+        g.bias = tensor_ptr(h, h->params, bias_index(h, l));   // add_col_vec, brnnet.py:141
         g.relu = (i <= h->NL && i != h->TL) ? 1 : 0;             // brnnet.py:155-157
-        g.prec = fwd_prec(h->cfg.operand_dtype);                 // SCTC_F16 -> forward: float16 operands
         if (fused_sum) {
             // hActs[TL] = hActsFor + hActsBack (brnnet.py:153) is formed while this GEMM stages its A operand;
             // the blocks of the first N tile store it to act[TL] for the weight gradient of this layer
@@ -523,39 +544,10 @@ static int run_forward(sctc_brnn* h, const sctc_minibatch* mb, hipStream_t s, Ph
                 g.skip_c32 = 1;
             }
         }
-        maybe_split(h, g);
-        SCTC_TRY(launch_gemm_f32(g, s));
+        SCTC_TRY(launch_gemm(h, g, s));
         if (i == h->TL) {
             pt.begin(SCTC_PHASE_FWD_REC);
-            RecArgs r;
-            memset(&r, 0, sizeof(r));
-            r.W[0] = tensor_ptr(h, h->params, wf_index(h));
-            r.W[1] = tensor_ptr(h, h->params, wb_index(h));
-            r.ldw = LD(h->Hp);
-            r.transpose = 0;
-            r.descending[0] = 0;
-            r.descending[1] = 1;
-            r.pre[0] = r.pre[1] = h->Z;
-            r.act[0] = r.act[1] = nullptr;
-            r.out[0] = h->hF;
-            r.out[1] = h->hB;
-            r.ld = LD(h->Hp);
-            r.Hp = h->Hp;
-            r.B = h->B;
-            r.Tmax = h->Tmax;
-            r.rowbase = h->d_rowbase;
-            r.T_b = h->d_Ts;
-            r.max_act = h->cfg.max_act;
-            r.xbuf = h->xbuf;
-            r.xbase = h->d_xbase;
-            r.n_xrows = (int)h->n_xrows;
-            r.counters = h->counters;
-            r.sync_mode = h->rec_sync_mode;
-            r.variant = h->rec_force_fallback ? REC_V_FALLBACK : h->rec_variant;
-            r.poll_delay = h->rec_poll_delay;
-            r.debug = h->rec_debug_on ? h->rec_debug : nullptr;
-            r.prec16 = h->cfg.operand_dtype == SCTC_F16;
-            r.T_host = h->Ts.data();
+            const RecArgs r = rec_args(h, false, h->Z);
             SCTC_TRY(launch_recurrent(r, s, &h->rec_path[0]));
             pt.begin(SCTC_PHASE_OTHER);
             // hActs[i] = hActsFor + hActsBack, brnnet.py:153
@@ -701,10 +693,8 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
         const float* W = h->params + wi.offset;
         // dW = deltasIn . hActs[i]^T (+ reg*W), brnnet.py:196-198
         {
-            GemmArgs g = gemm_defaults();
-            g.A = d_in;             // A(m=out, k=frame) = d_in[frame][out]
-            g.lda = d_in_ld;
-            g.a_kcontig = 0;
+            // A(m=out, k=frame) = d_in[frame][out], B(k=frame, n=in) = act[frame][in]
+            GemmArgs g = gemm_args({d_in, d_in_ld, 0}, {h->act[i], LD(inp), 0}, outp, inp, N, h->grads + wi.offset, LD(inp), bprec);
             if (fused_sum) {
                 // deltasOut = deltasFor + deltasBack (brnnet.py:233) is formed while this GEMM stages its A
                 // operand (its column sums, the bias gradient, are taken of the sum); the blocks of the first
@@ -714,29 +704,17 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
                 g.a_sum = const_cast<float*>(d_in);
                 fused_sum = false;
             }
-            g.B = h->act[i];        // B(k=frame, n=in) = act[frame][in]
-            g.ldb = LD(inp);
-            g.b_kcontig = 0;
-            g.M = outp;
-            g.N = inp;
-            g.K = (int)N;
-            g.C = h->grads + wi.offset;
-            g.ldc = LD(inp);
             g.accumulate = acc;
             if (reg > 0.f) { g.addend = W; g.ldadd = LD(inp); g.add_scale = reg; }
             // db = deltasIn.sum(axis=1), brnnet.py:200: column sums of the A operand, fused
             g.colsum_a = h->grads + h->tinfo[bias_index(h, i)].offset;
             g.splitk_ws = h->splitk_ws;
-            g.prec = bprec;
             if (h16) {
                 g.in16 = 1;
                 g.A = reinterpret_cast<const float*>(d_in16);
                 g.B = reinterpret_cast<const float*>(h->act16b[i]);
             }
-            int splits = 1;
-            gemm_plan_splits(g.M, g.N, g.K, &splits, g.prec, g.in16);
-            g.splits = splits;
-            SCTC_TRY(launch_gemm_f32(g, s));
+            SCTC_TRY(launch_gemm(h, g, s));
             // The weight gradients of the layers above the temporal layer (loop indices i >= TL: W_{TL+1}
             // .. W_{NL+1}) finish BEFORE the BPTT recurrence starts.  A collective
             // started on their event would hold compute units while the persistent BPTT grid is being
@@ -751,20 +729,9 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
         // deltasOut = W^T deltasIn, brnnet.py:204  (+ sign(hActs[i]) mask, :235-237)
         float* d_out = bufs[which];
         {
-            GemmArgs g = gemm_defaults();
-            g.A = d_in;             // [N][outp], K = outp
-            g.lda = d_in_ld;
-            g.a_kcontig = 1;
-            g.B = W;                // B(k=out, n=in) = W[out][in]
-            g.ldb = LD(inp);
-            g.b_kcontig = 0;
-            g.M = (int)N;
-            g.N = inp;
-            g.K = outp;
-            g.C = d_out;
-            g.ldc = LD(inp);
+            // A = d_in [N][outp], K = outp; B(k=out, n=in) = W[out][in]
+            GemmArgs g = gemm_args({d_in, d_in_ld, 1}, {W, LD(inp), 0}, N, inp, outp, d_out, LD(inp), bprec);
             if (i != h->TL) { g.mask = h->act[i]; g.ldmask = LD(h->Hp); }
-            g.prec = bprec;
             if (h16) {
                 g.in16 = 1;
                 g.A = reinterpret_cast<const float*>(d_in16);
@@ -783,41 +750,11 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
                     g.skip_c32 = 1;
                 }
             }
-            maybe_split(h, g);
-            SCTC_TRY(launch_gemm_f32(g, s));
+            SCTC_TRY(launch_gemm(h, g, s));
         }
         if (i == h->TL) {
             pt.begin(SCTC_PHASE_BWD_REC);
-            RecArgs r;
-            memset(&r, 0, sizeof(r));
-            r.W[0] = tensor_ptr(h, h->params, wf_index(h));
-            r.W[1] = tensor_ptr(h, h->params, wb_index(h));
-            r.ldw = LD(h->Hp);
-            r.transpose = 1;
-            r.descending[0] = 1;   // deltasFor runs from T-1 down, brnnet.py:217-218
-            r.descending[1] = 0;   // deltasBack runs from 0 up,    brnnet.py:219-220
-            r.pre[0] = r.pre[1] = d_out;
-            r.act[0] = h->hF;
-            r.act[1] = h->hB;
-            r.out[0] = h->dF;
-            r.out[1] = h->dBk;
-            r.ld = LD(h->Hp);
-            r.Hp = h->Hp;
-            r.B = h->B;
-            r.Tmax = h->Tmax;
-            r.rowbase = h->d_rowbase;
-            r.T_b = h->d_Ts;
-            r.max_act = h->cfg.max_act;
-            r.xbuf = h->xbuf;
-            r.xbase = h->d_xbase;
-            r.n_xrows = (int)h->n_xrows;
-            r.counters = h->counters;
-            r.sync_mode = h->rec_sync_mode;
-            r.variant = h->rec_force_fallback ? REC_V_FALLBACK : h->rec_variant;
-            r.poll_delay = h->rec_poll_delay;
-            r.debug = h->rec_debug_on ? h->rec_debug + REC_DEBUG_WORDS : nullptr;
-            r.prec16 = h->cfg.operand_dtype == SCTC_F16;
-            r.T_host = h->Ts.data();
+            const RecArgs r = rec_args(h, true, d_out);
             SCTC_TRY(launch_recurrent(r, s, &h->rec_path[1]));
             for (int l = h->NL; l >= h->TL; --l)     // the held-back events of the layers above (see there)
                 SCTC_HIP_TRY(hipEventRecord(h->grad_ev[weight_index(h, l)], s));
@@ -831,13 +768,8 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
             // (brnnet.py:227-230) over the (lo = frame t, hi = frame t+1) row pairs of every utterance
             for (int k = 0; k < 2; ++k) {
                 const sctc_tensor_info& ri = h->tinfo[k == 0 ? wf_index(h) : wb_index(h)];
-                GemmArgs g = gemm_defaults();
-                g.A = k == 0 ? h->dF : h->dBk;
-                g.lda = LD(h->Hp);
-                g.a_kcontig = 0;
-                g.B = k == 0 ? h->hF : h->hB;
-                g.ldb = LD(h->Hp);
-                g.b_kcontig = 0;
+                GemmArgs g = gemm_args({k == 0 ? h->dF : h->dBk, LD(h->Hp), 0}, {k == 0 ? h->hF : h->hB, LD(h->Hp), 0}, h->Hp, h->Hp,
+                                       h->npairs, h->grads + ri.offset, LD(h->Hp), bprec);
                 const uint16_t* a16 = k == 0 ? h->dF16b : h->dBk16b;
                 const uint16_t* b16 = k == 0 ? h->hF16b : h->hB16b;
                 if (h->pairs_contig) {
@@ -850,11 +782,6 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
                     g.idx_a = k == 0 ? h->d_idx_hi : h->d_idx_lo;
                     g.idx_b = k == 0 ? h->d_idx_lo : h->d_idx_hi;
                 }
-                g.M = h->Hp;
-                g.N = h->Hp;
-                g.K = (int)h->npairs;
-                g.C = h->grads + ri.offset;
-                g.ldc = LD(h->Hp);
                 g.accumulate = acc;
                 if (reg > 0.f) {           // brnnet.py:244-247
                     g.addend = h->params + ri.offset;
@@ -862,16 +789,12 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
                     g.add_scale = reg;
                 }
                 g.splitk_ws = h->splitk_ws;
-                g.prec = bprec;
                 if (h16) {
                     g.in16 = 1;
                     g.A = reinterpret_cast<const float*>(a16);
                     g.B = reinterpret_cast<const float*>(b16);
                 }
-                int splits = 1;
-                gemm_plan_splits(g.M, g.N, std::max(g.K, 1), &splits, g.prec, g.in16 && !g.idx_a);
-                g.splits = splits;
-                SCTC_TRY(launch_gemm_f32(g, s));
+                SCTC_TRY(launch_gemm(h, g, s));
                 SCTC_HIP_TRY(hipEventRecord(h->grad_ev[k == 0 ? wf_index(h) : wb_index(h)], s));
             }
             // deltasOut = deltasFor + deltasBack, brnnet.py:233

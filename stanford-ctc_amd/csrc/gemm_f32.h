@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_plan.h"
+
 namespace sctc {
 
 // C[M][N] (row-major, ldc) = sum_k A(m,k) * B(k,n)   then the epilogue.
@@ -97,18 +99,37 @@ __device__ __forceinline__ int gemm_xcd_tile(int nblk)
 }
 #endif
 
-// picks the split-K factor; returns the workspace floats needed (0 when splits == 1)
-int64_t gemm_plan_splits(int M, int N, int K, int* splits, int prec = 0, int in16 = 0);   // in16: operands 16-bit in memory, same layout
-int launch_gemm_f32(GemmArgs a, hipStream_t stream);     // dispatches on a.prec
-// gemm_h16.hip
-int64_t gemm_h16_plan_splits(int M, int N, int K, int* splits, int prec, int in16);
-int launch_gemm_h16_tiles(const GemmArgs& a, hipStream_t stream);
-// gemm_g16.hip: 16-bit operands in memory, staged by LDS-DMA (256 x 256 tiles)
-bool gemm_g16_applies(const GemmArgs& a);
-bool gemm_g16_enabled();
-int launch_gemm_g16(const GemmArgs& a, hipStream_t stream);
-// prec 3 (gemm_s3.hip)
-int64_t gemm_s3_plan_splits(int M, int N, int K, int* splits);
-int launch_gemm_s3(const GemmArgs& a, hipStream_t stream);
+// The plain facts of a call, for gemm_plan.h
+inline GemmQuery gemm_query(const GemmArgs& a)
+{
+    GemmQuery q;
+    q.M = a.M; q.N = a.N; q.K = a.K;
+    q.prec = a.prec; q.in16 = a.in16;
+    q.a_kcontig = a.a_kcontig; q.b_kcontig = a.b_kcontig;
+    q.idx_a = a.idx_a != nullptr; q.idx_b = a.idx_b != nullptr;
+    q.a2 = a.A2 != nullptr; q.a_sum = a.a_sum != nullptr;
+    q.lda_mod8 = (int)(a.lda % 8); q.ldb_mod8 = (int)(a.ldb % 8);
+    q.shadows = a.C16a || a.C16b;
+    q.skip_c32 = a.skip_c32 != 0; q.accumulate = a.accumulate != 0;
+    q.mask = a.mask != nullptr; q.mask16 = a.mask16 != nullptr;
+    q.ab_misaligned = (((uintptr_t)a.A | (uintptr_t)a.B) & 15) != 0;
+    q.a2_misaligned = (((uintptr_t)a.A2 | (uintptr_t)a.a_sum) & 15) != 0;
+    q.ldmask16_mod4 = (int)(a.ldmask16 % 4);
+    q.splits = a.splits;
+    q.workspace = a.splitk_ws != nullptr;
+    return q;
+}
+// the plan of a call under the process's current switches
+inline GemmPlan gemm_plan(const GemmArgs& a) { return gemm_plan(gemm_query(a), gemm_switches_from_env()); }
+
+// validate -> plan -> launch (-> the split-K reduce): a.splits K slices (1, or the plan's `splits` when the caller
+// has the plan's ws_floats in a.splitk_ws)
+int launch_gemm_f32(GemmArgs a, hipStream_t stream);
+// a plan's kernel: each source instantiates its own family
+typedef void (*GemmKernelFn)(GemmArgs);
+GemmKernelFn gemm_f32_kernel_for(const GemmPlan& p);    // GEMM_F32
+GemmKernelFn gemm_h16_kernel_for(const GemmPlan& p);    // GEMM_H16, GEMM_X16
+GemmKernelFn gemm_g16_kernel_for(const GemmPlan& p);    // GEMM_G16
+GemmKernelFn gemm_s3_kernel_for(const GemmPlan& p);     // GEMM_S3
 
 }  // namespace sctc

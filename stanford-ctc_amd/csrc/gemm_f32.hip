@@ -16,6 +16,9 @@
 // measured 100-105 TFLOP/s on the cfg-3 shapes vs 88-100 with BK = 32 / 2 blocks.
 // Workgroup ids are remapped so that the blocks of one XCD walk the N tiles of one
 // A row-panel consecutively (panel stays in that XCD's 4 MiB L2).
+#include <mutex>
+#include <set>
+
 #include "common.h"
 #include "gemm_f32.h"
 #include "gemm_h16_dev.h"     // h16_epilogue: the vectorised epilogue shared with the 16-bit kernels
@@ -357,77 +360,42 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs p)
     }
 }
 
-struct ShapeInfo { int bm, bn, occ; double penalty; };
-static const ShapeInfo kShapes[N_SHAPES] = {
-    {TileCfg<0>::BM, TileCfg<0>::BN, TileCfg<0>::OCC, 0.00},
-    {TileCfg<1>::BM, TileCfg<1>::BN, TileCfg<1>::OCC, 0.02},   // smaller tiles must save at least this much padded work
-    {TileCfg<2>::BM, TileCfg<2>::BN, TileCfg<2>::OCC, 0.10},
-    {TileCfg<3>::BM, TileCfg<3>::BN, TileCfg<3>::OCC, 0.10},
-};
-
-// tile shape with the least padded (wasted) matrix-core work for an M x N output
-int gemm_pick_shape(int M, int N)
-{
-    const char* force = getenv("SCTC_GEMM_SHAPE");   // diagnostics: 0 / 1
-    if (force) return std::max(0, std::min(N_SHAPES - 1, atoi(force)));
-    int best = 0;
-    double best_cost = 1e30;
-    for (int i = 0; i < N_SHAPES; ++i) {
-        const double pm = (double)((M + kShapes[i].bm - 1) / kShapes[i].bm * kShapes[i].bm) / M;
-        const double pn = (double)((N + kShapes[i].bn - 1) / kShapes[i].bn * kShapes[i].bn) / N;
-        const double cost = pm * pn + kShapes[i].penalty;
-        if (cost < best_cost - 1e-12) { best_cost = cost; best = i; }
-    }
-    return best;
-}
-
-int64_t gemm_plan_splits(int M, int N, int K, int* splits, int prec, int in16)
-{
-    if (prec) return gemm_h16_plan_splits(M, N, K, splits, prec, in16);
-    const ShapeInfo& sh = kShapes[gemm_pick_shape(M, N)];
-    const int mt = (M + sh.bm - 1) / sh.bm, nt = (N + sh.bn - 1) / sh.bn;
-    const int ktiles = (K + BK - 1) / BK;
-    int s = 1;
-    // 256 CUs x `occ` resident blocks.  A grid that is not a multiple of that leaves a partial
-    // last round (225 tiles x 3 splits = 675 blocks ran at 66 %); pick the split that fills
-    // whole rounds best, keeping >= 8 K tiles per split.
-    const int tiles = mt * nt, slots = 256 * sh.occ;
-    if (tiles < 2 * slots) {
-        double best = 0.0;
-        const int smax = std::min(64, std::max(1, ktiles / 8));
-        for (int c = 1; c <= smax; ++c) {
-            const int blocks = tiles * c;
-            const int rounds = (blocks + slots - 1) / slots;
-            // efficiency of the last round, mildly penalising the extra partial traffic
-            const double eff = (double)blocks / ((double)rounds * slots) - 0.002 * c;
-            if (eff > best + 1e-9) { best = eff; s = c; }
-        }
-    }
-    *splits = s;
-    return s > 1 ? (int64_t)s * M * (N + 1) : 0;   // + [splits][M] column-sum partials
-}
+// ------------------------------------------------------------------ host side
 
 template <int SHAPE>
-static int launch_tiles(GemmArgs a, hipStream_t stream)
+static GemmKernelFn f32_kernel_of_shape(const GemmPlan& p)
 {
-    constexpr int BM = TileCfg<SHAPE>::BM, BN_ = TileCfg<SHAPE>::BN;
-    const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN_ - 1) / BN_;
-    dim3 grid(mt * nt, a.splits), block(TileCfg<SHAPE>::NT);
-    const size_t smem = sizeof(float) * lds_floats(BM, BN_);  // 2 operands x 2 buffers
-    void (*kern)(GemmArgs) = nullptr;
-    if (a.A2) kern = a.a_kcontig ? gemm_f32_kernel<true, true, SHAPE, true> : gemm_f32_kernel<false, false, SHAPE, true>;
-    else if (a.a_kcontig && a.b_kcontig) kern = gemm_f32_kernel<true, true, SHAPE>;
-    else if (a.a_kcontig && !a.b_kcontig) kern = gemm_f32_kernel<true, false, SHAPE>;
-    else if (!a.a_kcontig && a.b_kcontig) kern = gemm_f32_kernel<false, true, SHAPE>;
-    else kern = gemm_f32_kernel<false, false, SHAPE>;
-    static bool attr_set[6] = {false, false, false, false, false, false};
-    const int vi = a.A2 ? 4 + (a.a_kcontig ? 1 : 0) : (a.a_kcontig ? 2 : 0) + (a.b_kcontig ? 1 : 0);
-    if (!attr_set[vi]) {
-        SCTC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set[vi] = true;
+    static_assert(TileCfg<SHAPE>::BM == gemm_shape(SHAPE).bm && TileCfg<SHAPE>::BN == gemm_shape(SHAPE).bn &&
+                  TileCfg<SHAPE>::OCC == gemm_shape(SHAPE).occ && TileCfg<SHAPE>::NT == 256 && BK == GEMM_F32_BK,
+                  "gemm_plan.h, gemm_shape: out of date");
+    if (p.a2) return p.ak ? gemm_f32_kernel<true, true, SHAPE, true> : gemm_f32_kernel<false, false, SHAPE, true>;
+    if (p.ak) return p.bkc ? gemm_f32_kernel<true, true, SHAPE> : gemm_f32_kernel<true, false, SHAPE>;
+    return p.bkc ? gemm_f32_kernel<false, true, SHAPE> : gemm_f32_kernel<false, false, SHAPE>;
+}
+
+GemmKernelFn gemm_f32_kernel_for(const GemmPlan& p)
+{
+    static_assert(N_SHAPES == GEMM_N_SHAPES, "gemm_plan.h, gemm_shape: out of date");
+    switch (p.shape) {
+        case 1: return f32_kernel_of_shape<1>(p);
+        case 2: return f32_kernel_of_shape<2>(p);
+        case 3: return f32_kernel_of_shape<3>(p);
+        default: return f32_kernel_of_shape<0>(p);
     }
-    hipLaunchKernelGGL(kern, grid, block, smem, stream, a);
+}
+
+// the one launch of every GEMM kernel: plan.grid_x tiles x a.splits K slices
+static int gemm_launch(GemmKernelFn kern, const GemmPlan& p, const GemmArgs& a, hipStream_t stream)
+{
+    if (p.lds_bytes > 64 * 1024) {   // beyond the default limit: raised once per kernel
+        static std::mutex mu;
+        static std::set<const void*> done;
+        std::lock_guard<std::mutex> lock(mu);
+        if (done.insert(reinterpret_cast<const void*>(kern)).second)
+            SCTC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes));
+    }
+    hipLaunchKernelGGL(kern, dim3(p.grid_x, a.splits), dim3(p.threads), p.lds_bytes, stream, a);
     SCTC_HIP_TRY(hipGetLastError());
     return SCTC_OK;
 }
@@ -435,44 +403,19 @@ static int launch_tiles(GemmArgs a, hipStream_t stream)
 int launch_gemm_f32(GemmArgs a, hipStream_t stream)
 {
     if (a.M <= 0 || a.N <= 0) return SCTC_OK;
-    SCTC_CHECK_ARG(a.K >= 0, "gemm: negative K");
-    SCTC_CHECK_ARG(a.lda % 4 == 0 && a.ldb % 4 == 0, "gemm: lda/ldb must be multiples of 4");
-    SCTC_CHECK_ARG(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.B & 15) == 0,
-                   "gemm: operands must be 16-byte aligned");
-    if (a.in16) {
-        SCTC_CHECK_ARG(a.prec != 0 && a.a_kcontig == a.b_kcontig && a.lda % 8 == 0 && a.ldb % 8 == 0 &&
-                           (!a.a_kcontig || a.K % 8 == 0),
-                       "gemm: 16-bit operands need prec != 0, equal operand layouts, lda/ldb % 8 == 0 "
-                       "and (K-contiguous) K % 8 == 0");
-    } else {
-        SCTC_CHECK_ARG((!a.C16a && !a.C16b) || a.prec != 0, "gemm: 16-bit shadow outputs need prec != 0");
-    }
-    SCTC_CHECK_ARG(!a.skip_c32 || ((a.C16a || a.C16b) && !a.accumulate && a.prec != 0),
-                   "gemm: skip_c32 needs a 16-bit shadow output, no accumulate and prec != 0");
-    SCTC_CHECK_ARG(!a.mask16 || (!a.mask && a.prec != 0 && a.ldmask16 % 4 == 0), "gemm: mask16 excludes mask, needs prec != 0");
-    if (a.a_kcontig) SCTC_CHECK_ARG(a.K % 4 == 0, "gemm: K must be a multiple of 4 (A K-contig)");
-    else SCTC_CHECK_ARG(a.M % 4 == 0, "gemm: M must be a multiple of 4 (A row-contig)");
-    if (a.b_kcontig) SCTC_CHECK_ARG(a.K % 4 == 0, "gemm: K must be a multiple of 4 (B K-contig)");
-    else SCTC_CHECK_ARG(a.N % 4 == 0, "gemm: N must be a multiple of 4 (B row-contig)");
-    SCTC_CHECK_ARG(!a.A2 || (a.prec == 0 && a.a_kcontig == a.b_kcontig && !a.idx_a && ((uintptr_t)a.A2 & 15) == 0 &&
-                              ((uintptr_t)a.a_sum & 15) == 0),
-                   "gemm: a two-addend A operand needs prec 0, layout NT or TN, no row gather, 16-byte alignment");
-    SCTC_CHECK_ARG(!a.a_sum || a.A2, "gemm: a_sum without A2");
     if (a.splits < 1) a.splits = 1;
-    if (a.splits > 1) SCTC_CHECK_ARG(a.splitk_ws != nullptr, "gemm: split-K without workspace");
-    if (a.prec) {
-        SCTC_CHECK_ARG(a.prec >= 1 && a.prec <= 3, "gemm: unknown operand precision %d", a.prec);
-        SCTC_CHECK_ARG(a.prec != 3 || (!a.in16 && !a.C16a && !a.C16b),
-                       "gemm: the three-term split takes fp32 operands and writes no 16-bit shadows");
-        SCTC_TRY(launch_gemm_h16_tiles(a, stream));
-    } else {
-        switch (gemm_pick_shape(a.M, a.N)) {
-            case 1: SCTC_TRY(launch_tiles<1>(a, stream)); break;
-            case 2: SCTC_TRY(launch_tiles<2>(a, stream)); break;
-            case 3: SCTC_TRY(launch_tiles<3>(a, stream)); break;
-            default: SCTC_TRY(launch_tiles<0>(a, stream)); break;
-        }
+    char why[160];
+    SCTC_CHECK_ARG(gemm_validate(gemm_query(a), why, sizeof(why)), "%s", why);
+    const GemmPlan p = gemm_plan(a);
+    GemmKernelFn kern = nullptr;
+    switch (p.kernel) {
+        case GEMM_F32: kern = gemm_f32_kernel_for(p); break;
+        case GEMM_H16:
+        case GEMM_X16: kern = gemm_h16_kernel_for(p); break;
+        case GEMM_G16: kern = gemm_g16_kernel_for(p); break;
+        case GEMM_S3: kern = gemm_s3_kernel_for(p); break;
     }
+    SCTC_TRY(gemm_launch(kern, p, a, stream));
     if (a.splits > 1) {
         const int64_t total = (int64_t)a.M * a.N;
         int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
@@ -531,11 +474,9 @@ static int gemm_entry(const float* A_dev, int64_t lda, int32_t a_kcontig, const 
     g.bias = bias_dev; g.relu = relu;
     g.prec = prec & 0xff;
     g.in16 = (prec & 0x100) ? 1 : 0;
-    prec &= 0xff;
-    int splits = 1;
-    const int64_t need = gemm_plan_splits(M, N, K, &splits, prec, g.in16 && a_kcontig == b_kcontig);
-    if (splits > 1 && workspace_dev && workspace_bytes >= (size_t)need * sizeof(float)) {
-        g.splits = splits;
+    const GemmPlan p = gemm_plan(g);
+    if (p.splits > 1 && workspace_dev && workspace_bytes >= (size_t)p.ws_floats * sizeof(float)) {
+        g.splits = p.splits;
         g.splitk_ws = (float*)workspace_dev;
     } else {
         g.splits = 1;

@@ -33,8 +33,6 @@
 // The fused bias gradient (column sums of a row-contiguous A, brnnet.py:200) is taken from the LDS
 // image by the blocks of the first N tile (fp32 sums of the 16-bit deltas, fixed order).
 #include <algorithm>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
 #include "common.h"
@@ -427,40 +425,12 @@ __global__ __launch_bounds__(G_NT, 2) void gemm_g16_kernel(GemmArgs p)
 
 // ------------------------------------------------------------------ host side
 
-bool gemm_g16_enabled()
+GemmKernelFn gemm_g16_kernel_for(const GemmPlan& p)
 {
-    static const int off = [] { const char* e = getenv("SCTC_G16"); return (e && atoi(e) == 0) ? 1 : 0; }();
-    return !off;                 // diagnostics: SCTC_G16=0 keeps round 2's register-staged kernel
-}
-
-bool gemm_g16_applies(const GemmArgs& a)
-{
-    if (!gemm_g16_enabled()) return false;
-    return a.in16 && (a.prec == 1 || a.prec == 2) && a.a_kcontig == a.b_kcontig && !a.idx_a && !a.idx_b &&
-           a.lda % 8 == 0 && a.ldb % 8 == 0 && (a.a_kcontig ? a.K % 8 == 0 : (a.M % 8 == 0 && a.N % 8 == 0));
-}
-
-int launch_gemm_g16(const GemmArgs& a, hipStream_t stream)
-{
-    const int mt = (a.M + G_BM - 1) / G_BM, nt = (a.N + G_BN - 1) / G_BN;
-    dim3 grid(mt * nt, a.splits), block(G_NT);
-    const bool bf = a.prec == 2;
-    void (*kern)(GemmArgs) = a.a_kcontig ? (bf ? gemm_g16_kernel<true, true> : gemm_g16_kernel<true, false>)
-                                         : (bf ? gemm_g16_kernel<false, true> : gemm_g16_kernel<false, false>);
-    const size_t smem = std::max<size_t>(G_NST * G_STB, G_EPI_LDS);
-    {
-        static std::mutex mu;
-        static std::set<const void*> done;
-        std::lock_guard<std::mutex> lock(mu);
-        if (!done.count(reinterpret_cast<const void*>(kern))) {
-            SCTC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            done.insert(reinterpret_cast<const void*>(kern));
-        }
-    }
-    hipLaunchKernelGGL(kern, grid, block, smem, stream, a);
-    SCTC_HIP_TRY(hipGetLastError());
-    return SCTC_OK;
+    static_assert(G_BM == gemm_h16_tile(true) && G_BN == G_BM && G_BK == GEMM_G16_BK && G_NT == 512 &&
+                  std::max(G_NST * G_STB, G_EPI_LDS) == GEMM_G16_LDS, "gemm_plan.h, GEMM_G16_*: out of date");
+    if (p.ak) return p.bf ? gemm_g16_kernel<true, true> : gemm_g16_kernel<true, false>;
+    return p.bf ? gemm_g16_kernel<false, true> : gemm_g16_kernel<false, false>;
 }
 
 }  // namespace sctc

@@ -26,8 +26,6 @@
 //   row-contiguous operand: every thread loads a 4(k) x 4(row) micro-tile, transposes it in registers
 //     (fp32: while converting; 16-bit: v_perm_b32) and writes 4 x ds_write_b64.
 #include <algorithm>
-#include <mutex>
-#include <set>
 #include <utility>
 
 #include "common.h"
@@ -379,94 +377,21 @@ __global__ __launch_bounds__(HTile<BIG>::NT, BIG ? 2 : X_OCC) void gemm_x16_kern
 
 // ------------------------------------------------------------------ host side
 
-// the 256x256 tile when the output is large enough to give every CU whole tiles of it and its
-// padding does not cost more than it saves (H = 1824 = 7.1 x 256 pads 12 %)
-static int h16_pick_big(int M, int N, int K, bool g16)
-{
-    const char* force = getenv("SCTC_H16_TILE");     // diagnostics: 0 / 1
-    if (force) return atoi(force) ? 1 : 0;
-    auto padded = [](int v, int t) { return (double)((v + t - 1) / t * t) / v; };
-    const double small = padded(M, 128) * padded(N, 128), big = padded(M, 256) * padded(N, 256);
-    const int64_t tiles_big = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
-    // the LDS-DMA kernel runs the long-K weight gradients at twice the rate of the 128 x 128 register-staged
-    // one (cfg-5 input layer, 2048 x 640 x 64000: 0.63 ms there): it may waste up to 25 % on padding
-    // and fills the machine through split-K
-    if (g16 && K >= 4096 && tiles_big >= 8 && big <= 1.25 * small) return 1;
-    return (tiles_big >= 32 && big <= 1.06 * small) ? 1 : 0;
-}
-
-int64_t gemm_h16_plan_splits(int M, int N, int K, int* splits, int prec, int in16)
-{
-    if (prec == 3) return gemm_s3_plan_splits(M, N, K, splits);
-    const int big = h16_pick_big(M, N, K, in16 && gemm_g16_enabled());
-    const int bm = big ? 256 : 128, occ = big ? 1 : 2;
-    const int mt = (M + bm - 1) / bm, nt = (N + bm - 1) / bm;
-    const int ktiles = (K + 63) / 64;
-    int s = 1;
-    // fill whole rounds of 256 CUs x `occ` resident blocks, >= 4 K tiles of 64 (256 k) per split
-    const int tiles = mt * nt, slots = 256 * occ;
-    if (tiles < 2 * slots) {
-        double best = 0.0;
-        const int smax = std::min(64, std::max(1, ktiles / 4));
-        for (int c = 1; c <= smax; ++c) {
-            const int blocks = tiles * c;
-            const int rounds = (blocks + slots - 1) / slots;
-            const double eff = (double)blocks / ((double)rounds * slots) - 0.002 * c;
-            if (eff > best + 1e-9) { best = eff; s = c; }
-        }
-    }
-    *splits = s;
-    return s > 1 ? (int64_t)s * M * (N + 1) : 0;
-}
-
-static int set_lds_once(void (*kern)(GemmArgs), size_t smem)
-{
-    if (smem <= 64 * 1024) return SCTC_OK;
-    static std::mutex mu;
-    static std::set<const void*> done;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!done.count(reinterpret_cast<const void*>(kern))) {
-        SCTC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        done.insert(reinterpret_cast<const void*>(kern));
-    }
-    return SCTC_OK;
-}
-
 template <int BIG>
-static int launch_h16(const GemmArgs& a, hipStream_t stream)
+static GemmKernelFn h16_kernel_of_tile(const GemmPlan& p)
 {
-    constexpr int BM = HTile<BIG>::BM, BN = HTile<BIG>::BN, NT = HTile<BIG>::NT;
-    const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
-    dim3 grid(mt * nt, a.splits), block(NT);
-    void (*kern)(GemmArgs) = nullptr;
-    const bool bf = a.prec == 2;
-    size_t smem;
-    if (a.in16) {     // both operands 16-bit in memory, same layout (checked by launch_gemm_f32)
-        smem = sizeof(unsigned short) * 2 * (BM + BN) * (64 + 8);
-        if (a.a_kcontig) kern = bf ? gemm_x16_kernel<true, true, BIG> : gemm_x16_kernel<true, false, BIG>;
-        else kern = bf ? gemm_x16_kernel<false, true, BIG> : gemm_x16_kernel<false, false, BIG>;
-    } else {
-        smem = sizeof(unsigned short) * 2 * (BM + BN) * (32 + 8);
-#define SCTC_H16_PICK(AKV, BKV)                                                              \
-    kern = bf ? gemm_h16_kernel<AKV, BKV, true, BIG> : gemm_h16_kernel<AKV, BKV, false, BIG>
-        if (a.a_kcontig && a.b_kcontig) SCTC_H16_PICK(true, true);
-        else if (a.a_kcontig && !a.b_kcontig) SCTC_H16_PICK(true, false);
-        else if (!a.a_kcontig && a.b_kcontig) SCTC_H16_PICK(false, true);
-        else SCTC_H16_PICK(false, false);
-#undef SCTC_H16_PICK
+    static_assert(HTile<BIG>::BM == gemm_h16_tile(BIG) && HTile<BIG>::BN == gemm_h16_tile(BIG) &&
+                  HTile<BIG>::NT == (BIG ? 512 : 256), "gemm_plan.h, gemm_h16_tile: out of date");
+    if (p.kernel == GEMM_X16) {     // both operands 16-bit in memory, same layout (gemm_validate)
+        if (p.ak) return p.bf ? gemm_x16_kernel<true, true, BIG> : gemm_x16_kernel<true, false, BIG>;
+        return p.bf ? gemm_x16_kernel<false, true, BIG> : gemm_x16_kernel<false, false, BIG>;
     }
-    SCTC_TRY(set_lds_once(kern, smem));
-    hipLaunchKernelGGL(kern, grid, block, smem, stream, a);
-    SCTC_HIP_TRY(hipGetLastError());
-    return SCTC_OK;
+#define SCTC_H16_PICK(AKV, BKV) (p.bf ? gemm_h16_kernel<AKV, BKV, true, BIG> : gemm_h16_kernel<AKV, BKV, false, BIG>)
+    if (p.ak) return p.bkc ? SCTC_H16_PICK(true, true) : SCTC_H16_PICK(true, false);
+    return p.bkc ? SCTC_H16_PICK(false, true) : SCTC_H16_PICK(false, false);
+#undef SCTC_H16_PICK
 }
 
-int launch_gemm_h16_tiles(const GemmArgs& a, hipStream_t stream)
-{
-    if (a.prec == 3) return launch_gemm_s3(a, stream);
-    if (h16_pick_big(a.M, a.N, a.K, gemm_g16_applies(a))) return gemm_g16_applies(a) ? launch_gemm_g16(a, stream) : launch_h16<1>(a, stream);
-    return launch_h16<0>(a, stream);
-}
+GemmKernelFn gemm_h16_kernel_for(const GemmPlan& p) { return p.big ? h16_kernel_of_tile<1>(p) : h16_kernel_of_tile<0>(p); }
 
 }  // namespace sctc

@@ -34,8 +34,6 @@
 // row stride), now a straight [k][m] copy read back with ds_read_b64_tr_b16; (4 k) x (2 rows) micro-tiles
 // with 8-byte global loads ran at 68 TFLOP/s (twice the load instructions).
 #include <algorithm>
-#include <mutex>
-#include <set>
 
 #include "common.h"
 #include "gemm_f32.h"
@@ -341,51 +339,14 @@ __global__ __launch_bounds__(S3_NT, 2) void gemm_s3_kernel(GemmArgs p)
 
 // ------------------------------------------------------------------ host side
 
-int64_t gemm_s3_plan_splits(int M, int N, int K, int* splits)
+GemmKernelFn gemm_s3_kernel_for(const GemmPlan& p)
 {
-    const int mt = (M + S3_BM - 1) / S3_BM, nt = (N + S3_BN - 1) / S3_BN;
-    const int ktiles = (K + 63) / 64;
-    int s = 1;
-    // fill whole rounds of 256 CUs x 2 resident blocks, >= 4 x 64 k per split
-    const int tiles = mt * nt, slots = 512;
-    if (tiles < 2 * slots) {
-        double best = 0.0;
-        const int smax = std::min(64, std::max(1, ktiles / 4));
-        for (int c = 1; c <= smax; ++c) {
-            const int blocks = tiles * c;
-            const int rounds = (blocks + slots - 1) / slots;
-            const double eff = (double)blocks / ((double)rounds * slots) - 0.002 * c;
-            if (eff > best + 1e-9) { best = eff; s = c; }
-        }
-    }
-    *splits = s;
-    return s > 1 ? (int64_t)s * M * (N + 1) : 0;
-}
-
-int launch_gemm_s3(const GemmArgs& a, hipStream_t stream)
-{
-    const int mt = (a.M + S3_BM - 1) / S3_BM, nt = (a.N + S3_BN - 1) / S3_BN;
-    dim3 grid(mt * nt, a.splits), block(S3_NT);
-    void (*kern)(GemmArgs) = nullptr;
-    constexpr size_t smem = sizeof(unsigned short) * 2 * S3_BUF;
-    const bool gather = (a.idx_a && !a.a_kcontig) || (a.idx_b && !a.b_kcontig);
-    if (a.a_kcontig && a.b_kcontig) kern = gemm_s3_kernel<true, true, false>;
-    else if (a.a_kcontig && !a.b_kcontig) kern = gather ? gemm_s3_kernel<true, false, true> : gemm_s3_kernel<true, false, false>;
-    else if (!a.a_kcontig && a.b_kcontig) kern = gather ? gemm_s3_kernel<false, true, true> : gemm_s3_kernel<false, true, false>;
-    else kern = gather ? gemm_s3_kernel<false, false, true> : gemm_s3_kernel<false, false, false>;
-    {
-        static std::mutex mu;
-        static std::set<const void*> done;
-        std::lock_guard<std::mutex> lock(mu);
-        if (!done.count(reinterpret_cast<const void*>(kern))) {
-            SCTC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            done.insert(reinterpret_cast<const void*>(kern));
-        }
-    }
-    hipLaunchKernelGGL(kern, grid, block, smem, stream, a);
-    SCTC_HIP_TRY(hipGetLastError());
-    return SCTC_OK;
+    static_assert(S3_BM == GEMM_S3_TILE && S3_BN == GEMM_S3_TILE && S3_BK == GEMM_S3_BK && S3_NT == 256 &&
+                  sizeof(unsigned short) * 2 * S3_BUF == GEMM_S3_LDS, "gemm_plan.h, GEMM_S3_*: out of date");
+    const bool g = p.gather;      // the K-contiguous pair has no row to gather
+    if (p.ak) return p.bkc ? gemm_s3_kernel<true, true, false> : (g ? gemm_s3_kernel<true, false, true> : gemm_s3_kernel<true, false, false>);
+    if (p.bkc) return g ? gemm_s3_kernel<false, true, true> : gemm_s3_kernel<false, true, false>;
+    return g ? gemm_s3_kernel<false, false, true> : gemm_s3_kernel<false, false, false>;
 }
 
 }  // namespace sctc

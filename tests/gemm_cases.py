@@ -32,16 +32,16 @@ IMPLS = {
     "bf16_round_tile1": dict(env={"SCTC_H16_TILE": "1"}, prec=2, in16=0, tile=(256, 256, 32)),
     "f16_mem_tile0": dict(env={"SCTC_H16_TILE": "0"}, prec=1, in16=1, tile=(128, 128, 64)),
     "bf16_mem_tile0": dict(env={"SCTC_H16_TILE": "0"}, prec=2, in16=1, tile=(128, 128, 64)),
-    # the LDS-DMA kernel (K tile 32) where gemm_g16_applies, else the register-staged 256 tile (K tile 64)
+    # the LDS-DMA kernel (K tile 32) where csrc/gemm_plan.h picks GEMM_G16, else the register-staged 256 tile (K tile 64)
     "f16_mem_tile1": dict(env={"SCTC_H16_TILE": "1"}, prec=1, in16=1, tile=(256, 256, 32)),
     "bf16_mem_tile1": dict(env={"SCTC_H16_TILE": "1"}, prec=2, in16=1, tile=(256, 256, 32)),
     "bf16x3": dict(env={"SCTC_H16_TILE": "0"}, prec=3, in16=0, tile=(128, 128, 16)),
 }
-ENV_NAMES = ("SCTC_GEMM_SHAPE", "SCTC_H16_TILE")     # never SCTC_G16: cached per process
+ENV_NAMES = ("SCTC_GEMM_SHAPE", "SCTC_H16_TILE", "SCTC_G16")
 
 
 def case_tile(c):
-    """(BM, BN, K tile) of the kernel that runs case c"""
+    """(BM, BN, K tile) of the kernel that runs case c; held against csrc/gemm_plan.h by tests/test_gemm_plan_cpu.py"""
     im = IMPLS[c.impl]
     bm, bn, bk = im["tile"]
     if im["in16"] and bm == 256:

@@ -88,9 +88,7 @@ def planned_splits(diag, monkeypatch, c):
         monkeypatch.delenv(n, raising=False)
     for n, v in im["env"].items():
         monkeypatch.setenv(n, v)
-    s = ctypes.c_int32(0)
-    diag.lib().sctc_diag_gemm_plan_splits(c.M, c.N, c.K, im["prec"], im["in16"], ctypes.byref(s))
-    return s.value
+    return diag.gemm_plan(c.M, c.N, c.K, c.lay, im["prec"], im["in16"], "gather" in c.opts, "a2" in c.opts).splits
 
 
 @pytest.mark.parametrize("impl", sorted(gc.IMPLS))
@@ -171,11 +169,10 @@ def test_planner_can_leave_the_last_slice_empty(libs, monkeypatch):
     last one starts at tile 81"""
     _, diag = libs
     monkeypatch.setenv("SCTC_GEMM_SHAPE", "0")
-    s = ctypes.c_int32(0)
-    need = diag.lib().sctc_diag_gemm_plan_splits(19 * 128, 4 * 128, 1296, 0, 0, ctypes.byref(s))
-    assert s.value == 10 and need == 10 * 19 * 128 * (4 * 128 + 1)
-    per = (81 + s.value - 1) // s.value
-    assert (s.value - 1) * per >= 81
+    p = diag.gemm_plan(19 * 128, 4 * 128, 1296, "TN", 0, 0)
+    assert p.splits == 10 and p.ws_floats == 10 * 19 * 128 * (4 * 128 + 1)
+    per = (81 + p.splits - 1) // p.splits
+    assert (p.splits - 1) * per >= 81
 
 
 # ---------------------------------------------------------------- rejections (no GPU: checked before any launch)

@@ -846,3 +846,28 @@ def test_tiled_recurrence_rows_equal_minibatches_of_32(mods, monkeypatch, H, B, 
          % (H, B, n_equal, n_seen))
     assert n_equal > 0
 
+
+
+@pytest.mark.parametrize("T_b", [(5,), (3,), (5, 3)], ids=["contiguous5", "contiguous3", "gathered"])
+def test_gradients_do_not_depend_on_the_frames_the_handle_was_sized_for(mods, T_b):
+    """The split-K workspace is sized at create time from plans for K = max_frames (csrc/gemm_plan.h,
+    brnn_splitk_floats), the launches plan again for their own K: a handle created for 8192 frames -- beyond the
+    K >= 4096 rule of the 16-bit tile choice and 1024 times the launch's K -- gives the gradients, bit for bit, of one
+    created for the 10 frames it needs.  One utterance pairs contiguous rows in the recurrent weight gradients, the
+    ragged pair gathers them."""
+    _sctc, brnnet, obrnn, torch = mods
+    D, A, H, NL, TL = 20, 6, 64, 2, 1
+    rs = np.random.RandomState(7)
+    data = [rs.randn(D, T) for T in T_b]
+    labels = [np.array([1, 2], dtype=np.int32)[:min(2, T)] for T in T_b]
+    got = []
+    for maxBatch in (5, 4096):
+        np.random.seed(11)
+        net = brnnet.NNet(D, A, H, NL, maxBatch, temporalLayer=TL, maxUtts=2)
+        net.initParams()
+        cost, _, skip = net.costAndGradBatch(data, labels)
+        assert not skip.any()
+        got.append((cost.copy(), net._grads.clone()))
+        assert bool(torch.isfinite(got[-1][1]).all()) and float(got[-1][1].abs().max()) > 0
+    assert np.array_equal(got[0][0], got[1][0])
+    assert torch.equal(got[0][1], got[1][1])

@@ -74,9 +74,8 @@ def _launch(mods, c, d):
     out = dict(C=dev(d.C0), C16a=dev(d.C16a0), C16b=dev(d.C16b0), colsum=dev(d.colsum0), asum=dev(d.asum0))
     splits, ws_floats = c.splits, c.splits * c.M * (c.N + 1)
     if "planner" in c.opts:
-        s = ctypes.c_int32(0)
-        ws_floats = D.sctc_diag_gemm_plan_splits(c.M, c.N, c.K, im["prec"], im["in16"], ctypes.byref(s))
-        splits = s.value
+        p = diag.gemm_plan(c.M, c.N, c.K, c.lay, im["prec"], im["in16"], "gather" in c.opts, "a2" in c.opts)
+        splits, ws_floats = p.splits, p.ws_floats
         assert splits > 1 and ws_floats == splits * c.M * (c.N + 1), (c.name, splits, ws_floats)
     ws = None
     if splits > 1:
@@ -138,9 +137,8 @@ def test_planner_leaves_the_last_slice_empty_and_the_kernels_cope(mods, monkeypa
     tile 81.  The same K and count on a small output are in every fp32 table (...-TN-...x1296-s10-...)."""
     _, diag, _ = mods
     monkeypatch.setenv("SCTC_GEMM_SHAPE", "0")
-    s = ctypes.c_int32(0)
-    diag.lib().sctc_diag_gemm_plan_splits(19 * 128, 4 * 128, 1296, 0, 0, ctypes.byref(s))
-    assert s.value == 10 and (s.value - 1) * ((81 + s.value - 1) // s.value) >= 81
+    s = diag.gemm_plan(19 * 128, 4 * 128, 1296, "TN", 0, 0).splits
+    assert s == 10 and (s - 1) * ((81 + s - 1) // s) >= 81
     for impl in ("f32_shape0", "f32_shape1", "f32_shape2", "f32_shape3"):
         assert any(c.K == 1296 and c.splits == 10 for c in gc.cases_for(impl))
 

@@ -81,8 +81,17 @@ typedef struct sctc_diag_gemm_args {
     float* a_sum;
 } sctc_diag_gemm_args;
 int sctc_diag_gemm(const sctc_diag_gemm_args* args, void* stream);
-/* sctc::gemm_plan_splits: the split-K count the product picks for this shape (through *splits) and the
- * workspace floats it needs (0 when *splits == 1) */
+/* sctc::gemm_plan (stanford-ctc_amd/csrc/gemm_plan.h) of these arguments under the process's current switches: what
+ * sctc_diag_gemm would launch (no pointer is dereferenced, no GPU needed).  kernel: 0 fp32, 1 16-bit rounding in
+ * registers, 2 16-bit operands staged through registers, 3 LDS-DMA, 4 bf16x3; splits / ws_floats: the split-K count
+ * the product picks and the workspace floats it needs (0 when splits == 1). */
+typedef struct sctc_diag_gemm_plan_out {
+    int32_t kernel, bm, bn, bk, threads, occ, lds_bytes, grid_x, splits, split_tile_differs;
+    int64_t ws_floats;
+} sctc_diag_gemm_plan_out;
+int sctc_diag_gemm_plan(const sctc_diag_gemm_args* args, sctc_diag_gemm_plan_out* out);
+/* the same plan asked by shape alone (both operands row-contiguous, no gather): the split-K count through *splits, the
+ * workspace floats it needs (0 when *splits == 1) returned */
 int64_t sctc_diag_gemm_plan_splits(int32_t M, int32_t N, int32_t K, int32_t prec, int32_t in16, int32_t* splits);
 
 /* ---- test-only door to the internal launchers of stanford-ctc_amd/csrc/elementwise.h (elementwise_entry.hip;

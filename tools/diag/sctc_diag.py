@@ -28,6 +28,25 @@ class GemmArgs(ctypes.Structure):
                 ("A2", ctypes.c_void_p), ("a_sum", ctypes.c_void_p)]
 
 
+class GemmPlan(ctypes.Structure):
+    """sctc_diag_gemm_plan_out of sctc_diag.h: sctc::GemmPlan (csrc/gemm_plan.h) without the template selectors"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "bm", "bn", "bk", "threads", "occ", "lds_bytes", "grid_x", "splits",
+                                              "split_tile_differs")] + [("ws_floats", ctypes.c_int64)]
+
+
+def gemm_plan(M, N, K, lay, prec, in16, gather=False, a2=False):
+    """the product's plan for a GEMM of this shape, layout ("NT": A K-contiguous, B K-contiguous; "TN": both
+    row-contiguous) and precision with leading dimensions that are multiples of 8, under the current environment"""
+    P = 0x10000                 # a 16-byte aligned address that is never dereferenced
+    akc, bkc = int(lay[0] == "N"), int(lay[1] == "T")
+    a = GemmArgs(A=P, B=P, C=P, lda=8, ldb=8, ldc=8, M=M, N=N, K=K, a_kcontig=akc, b_kcontig=bkc, splits=1, prec=prec, in16=in16,
+                 idx_a=P if gather and not akc else None, idx_b=P if gather and not bkc else None, A2=P if a2 else None)
+    out = GemmPlan()
+    rc = lib().sctc_diag_gemm_plan(ctypes.byref(a), ctypes.byref(out))
+    assert rc == 0
+    return out
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -49,6 +68,7 @@ def lib():
         L.sctc_diag_where.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_void_p]
         L.sctc_diag_gemm.argtypes = [ctypes.POINTER(GemmArgs), ctypes.c_void_p]
+        L.sctc_diag_gemm_plan.argtypes = [ctypes.POINTER(GemmArgs), ctypes.POINTER(GemmPlan)]
         L.sctc_diag_gemm_plan_splits.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)]
         L.sctc_diag_gemm_plan_splits.restype = ctypes.c_int64
         # the internal launchers of csrc/elementwise.h (elementwise_entry.hip); pointers as plain addresses
