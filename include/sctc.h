@@ -618,11 +618,21 @@ int sctc_brnn_set_ctc_workspace(sctc_brnn_t h, void* workspace_dev, size_t works
 #define SCTC_N_PHASES 6
 int sctc_brnn_set_profiling(sctc_brnn_t h, int32_t enable);
 /* diagnostics only: device pointer / shape of an internal fp32 matrix of the last call (which:
- * 0..numLayers = hActs[i] (0 = the packed input), 100 / 101 = hActsFor / hActsBack, 200 = the delta
- * entering layer 1); rows follow the packed time-major layout (one utterance: row t = frame t).
- * Lets a test separate the error of one contraction from the error of its operands. */
+ * 0..numLayers = hActs[i] (0 = the packed input), 100 / 101 = hActsFor / hActsBack, 102 = the temporal
+ * layer's W h + b, 200 = the delta entering layer 1, 201 / 202 = deltasFor / deltasBack as the BPTT
+ * recurrence left them); rows follow the packed time-major layout (one utterance: row t = frame t).
+ * Lets a test separate the error of one contraction from the error of its operands.  With
+ * operand_dtype = SCTC_F16 the hidden ReLU layers (1..numLayers) and 200 have no fp32 copy: see below. */
 int sctc_brnn_debug_buffer(sctc_brnn_t h, int32_t which, void** dev_ptr, int64_t* rows, int64_t* cols,
                            int64_t* ld);
+/* diagnostics only, operand_dtype = SCTC_F16: the 16-bit shadows the GEMMs read, as raw uint16 in the same
+ * layout; *dtype says how to read them.  SCTC_F16: which = 0..numLayers, the forward operands hActs[i].
+ * SCTC_BF16 (training models, after a cost_and_grad call): 50..50+numLayers = the weight gradients' copies
+ * of hActs[i], 100 / 101 = hActsFor / hActsBack, 200 = the delta entering layer 1, 201 / 202 = deltasFor /
+ * deltasBack, 203 = what the other of the two alternating delta buffers was left with (the delta entering
+ * layer 2). */
+int sctc_brnn_debug_buffer16(sctc_brnn_t h, int32_t which, void** dev_ptr, int64_t* rows, int64_t* cols,
+                             int64_t* ld, int32_t* dtype);
 /* diagnostics only: per-step s_memtime stamps of the recurrent kernel when SCTC_REC_DEBUG=1 */
 int sctc_brnn_debug_read(sctc_brnn_t h, uint32_t* out, int32_t n_words);
 int sctc_brnn_phase_ms(sctc_brnn_t h, float* ms_out /* [SCTC_N_PHASES] */);

@@ -59,7 +59,13 @@ class Mixed:
     time-batched contraction rounds BOTH operands to 16 bit (float16 in the forward pass,
     bfloat16 in the backward pass) and accumulates exactly; `rec` says whether the recurrent
     time step does the same (the 6..16-utterance kernel) or stays fp32 (the other kernels).
-    Everything else -- biases, clips, masks, softmax, CTC -- is unrounded."""
+    Where it rounds, in the backward pass: a delta matrix is rounded ONCE, and all its readers
+    take that bfloat16 copy -- the weight gradient, the next delta GEMM, and the BIAS GRADIENT,
+    which the device forms as the column sums of the weight-gradient GEMM's delta operand
+    (db = round_bf16(delta).sum, not delta.sum).  The recurrent state of BPTT is kept unrounded
+    (the temporal layer's own delta enters it unrounded); with rec=True only the copy the next
+    step reads, and W^T, are rounded.  Everything else -- bias values, clips, masks, softmax,
+    CTC -- is unrounded."""
 
     def __init__(self, rec=True):
         self.rec = rec
@@ -79,6 +85,9 @@ class Mixed:
     def bwd(self, a, b):
         return round_bf16(a) @ round_bf16(b)
 
+    def colsum(self, a):
+        return round_bf16(a).sum(axis=1, keepdims=True)
+
     def rec_fwd(self, w, x):
         return self._w(w, round_f16) @ round_f16(x) if self.rec else w @ x
 
@@ -93,6 +102,10 @@ class _Exact:
     def fwd(a, b):
         return a @ b
     bwd = rec_fwd = rec_bwd = fwd
+
+    @staticmethod
+    def colsum(a):
+        return a.sum(axis=1, keepdims=True)
 
 
 def _clip(x, max_act):
@@ -188,7 +201,7 @@ def cost_and_grad(params, data, labels, temporal_layer, max_act=20.0, reg=0.0, b
         dW[i] = mp.bwd(d_in, acts[i].T)
         if reg > 0:
             dW[i] = dW[i] + reg * W[i]
-        db[i] = d_in.sum(axis=1, keepdims=True)
+        db[i] = mp.colsum(d_in)
         if i == 0:
             break
         d_out = mp.bwd(W[i].T, d_in)

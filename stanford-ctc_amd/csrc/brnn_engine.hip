@@ -123,6 +123,7 @@ struct sctc_brnn {
     int rec_path[2] = {0, 0};     // REC_PATH_* of the last forward / BPTT recurrence
     int rec_retries = 0;          // steps of this handle that were re-run after SCTC_ERR_TIMEOUT
     const float* last_delta1 = nullptr;   // delta entering layer 1 (A operand of the dW1 GEMM) of the last backward pass
+    const uint16_t* last_delta1_16 = nullptr;   // its bfloat16 shadow (fp16-operand configuration)
     // host staging of the CTC descriptors (must outlive the async uploads)
     void* ctc_stage = nullptr;
     PinnedStage plan_stage;    // make_plan's uploads
@@ -810,6 +811,7 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
         which ^= 1;
     }
     h->last_delta1 = d_in;
+    h->last_delta1_16 = h16 ? d_in16 : nullptr;
     return SCTC_OK;
 }
 
@@ -1189,11 +1191,44 @@ int sctc_brnn_debug_buffer(sctc_brnn_t h, int32_t which, void** dev_ptr, int64_t
     else if (which == 101) p = h->hB;
     else if (which == 102) p = h->Z;
     else if (which == 200) p = h->last_delta1;
-    SCTC_CHECK_ARG(p, "debug_buffer: no buffer %d (layers 0..%d, 100 hF, 101 hB, 102 z of the temporal layer, 200 delta_1)", which, h->NL);
+    else if (which == 201) p = h->dF;
+    else if (which == 202) p = h->dBk;
+    SCTC_CHECK_ARG(p, "debug_buffer: no buffer %d (layers 0..%d, 100 hF, 101 hB, 102 z of the temporal layer, 200 delta_1, "
+                   "201 / 202 the BPTT outputs deltasFor / deltasBack)", which, h->NL);
     *dev_ptr = (void*)p;
     *rows = h->N;
     *cols = c;
     *ld = l;
+    return SCTC_OK;
+}
+
+/* diagnostics: the 16-bit shadows of the fp16-operand configuration after the LAST call, same row layout */
+int sctc_brnn_debug_buffer16(sctc_brnn_t h, int32_t which, void** dev_ptr, int64_t* rows, int64_t* cols,
+                             int64_t* ld, int32_t* dtype)
+{
+    SCTC_CHECK_ARG(h && dev_ptr && rows && cols && ld && dtype, "debug_buffer16: null argument");
+    SCTC_CHECK_ARG(h->cfg.operand_dtype == SCTC_F16, "debug_buffer16: only the fp16-operand configuration keeps 16-bit shadows");
+    const uint16_t* p = nullptr;
+    int64_t c = h->Hp, l = LD(h->Hp);
+    int32_t dt = SCTC_BF16;
+    if (which >= 0 && which <= h->NL) { p = h->act16f[which]; dt = SCTC_F16; }
+    else if (which >= 50 && which <= 50 + h->NL) p = h->act16b[which - 50];
+    else if (which == 100) p = h->hF16b;
+    else if (which == 101) p = h->hB16b;
+    else if (which == 200) p = h->last_delta1_16;
+    else if (which == 201) p = h->dF16b;
+    else if (which == 202) p = h->dBk16b;
+    else if (which == 203 && h->NL >= 2 && h->last_delta1_16)      // (one layer: the other buffer is never written)
+        p = h->last_delta1_16 == h->dA16 ? h->dBuf16 : h->dA16;
+    if (which == 0 || which == 50) { c = h->Dp; l = LD(h->Dp); }
+    SCTC_CHECK_ARG(p, "debug_buffer16: no buffer %d (0..%d float16 / 50..%d bfloat16 shadows of hActs[i]; bfloat16: 100 hF, 101 hB, "
+                   "200 delta_1, 201 deltasFor, 202 deltasBack, 203 the delta the other ping-pong buffer was left with; the "
+                   "bfloat16 ones exist in a training model after a cost_and_grad call)", which, h->NL, 50 + h->NL);
+    *dev_ptr = (void*)p;
+    *rows = h->N;
+    *cols = c;
+    *ld = l;
+    *dtype = dt;
     return SCTC_OK;
 }
 

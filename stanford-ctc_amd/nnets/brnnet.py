@@ -400,7 +400,8 @@ class NNet:
 
     def debugBuffer(self, which):
         """diagnostics: host copy (float64, [rows][cols]) of an internal matrix of the last call --
-        which: 0..numLayers = hActs[i], 100 / 101 = hActsFor / hActsBack, 102 = the temporal layer's W h + b, 200 = delta entering layer 1"""
+        which: 0..numLayers = hActs[i], 100 / 101 = hActsFor / hActsBack, 102 = the temporal layer's W h + b, 200 = delta entering
+        layer 1, 201 / 202 = deltasFor / deltasBack (the BPTT recurrence's outputs)"""
         torch = _sctc.require_gpu()
         ptr, rows, cols, ld = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _sctc.check(_sctc.lib().sctc_brnn_debug_buffer(self._h, which, ctypes.byref(ptr), ctypes.byref(rows),
@@ -409,6 +410,21 @@ class NNet:
         off = (ptr.value - self._ws.data_ptr()) // 4
         flat = self._ws.view(torch.float32)[off:off + rows.value * ld.value]
         return flat.view(rows.value, ld.value)[:, :cols.value].cpu().numpy().astype(np.float64)
+
+    def debugBuffer16(self, which):
+        """diagnostics, fp16=True only: (raw uint16 host copy [rows][cols], "float16" | "bfloat16") of a 16-bit shadow of the last
+        call -- which: 0..numLayers = the float16 hActs[i]; bfloat16: 50 + i = hActs[i], 100 / 101 = hActsFor / hActsBack,
+        200 = delta entering layer 1, 201 / 202 = deltasFor / deltasBack, 203 = delta entering layer 2"""
+        torch = _sctc.require_gpu()
+        ptr, rows, cols, ld = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        dt = ctypes.c_int32()
+        _sctc.check(_sctc.lib().sctc_brnn_debug_buffer16(self._h, which, ctypes.byref(ptr), ctypes.byref(rows), ctypes.byref(cols),
+                                                         ctypes.byref(ld), ctypes.byref(dt)), "debugBuffer16")
+        torch.cuda.synchronize()
+        off = (ptr.value - self._ws.data_ptr()) // 2
+        flat = self._ws.view(torch.int16)[off:off + rows.value * ld.value]
+        bits = flat.view(rows.value, ld.value)[:, :cols.value].contiguous().cpu().numpy().view(np.uint16)
+        return bits, {_sctc.F16: "float16", _sctc.BF16: "bfloat16"}[dt.value]
 
     def gradBuckets(self):
         """[(event, start, end)] over the flat gradient buffer in the order the backward pass

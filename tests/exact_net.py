@@ -10,15 +10,19 @@ implementations, and the backward pass is a fixed linear map of the CTC delta.
 make_case()   one case, with the conditions that keep it from being vacuous asserted on the float64 reference alone
 reference()   forward and (given oracle.ctc's per-utterance deltas) backward pass, one (H x H) @ (H x B_active)
               product per time step and direction instead of a loop over utterances
+Rounding      where the fp16-operand configuration rounds in its backward pass; reference(mixed=Rounding(..)) restates it:
+              with float64 accumulation it is the model the device is compared with, with float32 its noise estimate
 GPU_CASES     the matrix of tests/test_gpu_recurrence_exact.py (the CPU suite checks make_case's conditions on it)
-and the two comparisons both suites use: forward_rows_differing() (bit equality after the cast to float32, counted
-per (utterance, frame) row) and row_errors() (per-frame relative error of a delta matrix).
+and the comparisons both suites use: forward_rows_differing() (bit equality after the cast to float32, counted per
+(utterance, frame) row), row_errors() (per-frame relative error of a delta matrix) and, for the fp16-operand backward
+pass, mixed_stats() / mixed_e_ref() / mixed_violations().
 
 Columns of every internal matrix are PACKED time-major like the engine's rows: frame t of the utterance with length
 rank r (stable sort by length, longest first) is column rowbase[t] + r, so the utterances alive at a step are one
 contiguous slice.  What reference() returns is per utterance, in the caller's order, in the oracle's (features, T)
 layout.
 """
+import collections
 import functools
 from types import SimpleNamespace
 
@@ -278,12 +282,85 @@ def _ctc(case, fwd):
     return costs, delta, skips
 
 
-def _backward(case, fwd, delta, dtype, mutant):
-    """packed backward pass in `dtype` from the float64 forward reference and CTC delta"""
-    p, pl, TL, NL, mx = case.params, case.plan, case.TL, case.NL, case.max_act
-    name = mutant[0] if mutant else None
+class Rounding(collections.namedtuple("Rounding", "rec16 delta state16 db16 skip")):
+    """Where the backward pass of the fp16-operand configuration (NNet(fp16=True), SCTC_F16) rounds, read off run_backward
+    (csrc/brnn_engine.hip), add16_kernel / cvt16_kernel (csrc/elementwise.hip) and brnn_recurrent_mh_kernel
+    (csrc/recurrent.hip).  Every rounding is to nearest even; every product is exact; sums are in the accumulation type.
+
+    Always:  every delta matrix a GEMM reads -- dlogits, the ReLU-masked output of a delta GEMM, deltasFor + deltasBack
+             (summed in the accumulation type first), deltasFor and deltasBack themselves -- is read through ONE bfloat16
+             shadow, by the weight gradient (A operand), by the next delta GEMM (A operand) and by the bias gradient, which
+             is that GEMM's column sum of its A operand; the B operands are bfloat16 too: hActs[i], hActsFor / hActsBack,
+             W^T.
+    rec16    the BPTT recurrence keeps its state, its additive term (the temporal layer's delta, straight from the delta
+             GEMM's accumulator) and its result in the accumulation type; with the 16-bit exchange kernel (6..16
+             utterances) the state it READS from the previous step and the stationary W^T are bfloat16, with every other
+             recurrent kernel they are not rounded.
+    The remaining fields are what a correct device does; tests/test_exact_net_cpu.py changes one at a time:
+    delta    "bf16" | "trunc" (bfloat16 by truncation) | "f16" (float16 shadows of the deltas: 5 exponent bits)
+    state16  the BPTT state itself stored rounded        db16   bias gradients summed from the shadow (else: unrounded)
+    skip     one operand of one GEMM left unrounded: ("dW", i, "A" | "B"), ("dgrad", i, "A"), ("dWf" | "dWb", "A")"""
+    __slots__ = ()
+
+    def __new__(cls, rec16, delta="bf16", state16=False, db16=True, skip=None):
+        return super().__new__(cls, bool(rec16), delta, state16, db16, skip)
+
+
+def trunc_bf16(x):
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)
+    return u.view(np.float32).astype(np.float64).reshape(np.shape(x))
+
+
+# backward mutants that are a changed Rounding record: name -> fields (rec16 is flipped by "rec_flip")
+_ROUNDING_MUTANTS = {"trunc": {"delta": "trunc"}, "f16_shadow": {"delta": "f16"}, "state16": {"state16": True},
+                     "db_unrounded": {"db16": False}}
+
+
+def _mutated(mixed, name, arg):
+    if mixed is None or name is None:
+        return mixed
+    if name == "rec_flip":
+        return mixed._replace(rec16=not mixed.rec16)
+    if name == "unrounded":
+        return mixed._replace(skip=arg)
+    return mixed._replace(**_ROUNDING_MUTANTS.get(name, {}))
+
+
+def pair_rows(pl, shifted=None):
+    """(lo, hi): the packed rows of frames (t - 1, t) of every utterance, t = 1 .. T_b - 1, in the engine's order.  shifted
+    (a mutant): caller utterance whose pairs are taken one frame late, (t, t + 1), by the same index arithmetic -- past its
+    own last frame that is the row of whoever is packed there"""
     rb, nact, Tmax = pl.rowbase, pl.nact, pl.Tmax
-    cast = lambda m: np.ascontiguousarray(m, dtype=dtype)
+    hi = np.concatenate([rb[t] + np.arange(nact[t]) for t in range(1, Tmax)] + [np.zeros(0, dtype=np.int64)]).astype(np.int64)
+    lo = np.concatenate([rb[t - 1] + np.arange(nact[t]) for t in range(1, Tmax)] + [np.zeros(0, dtype=np.int64)]).astype(np.int64)
+    if shifted is not None:
+        r, T = pl.rank[shifted], pl.Ts[shifted]
+        assert T > 1
+        sel = np.concatenate([(np.arange(nact[t]) == r) for t in range(1, Tmax)])
+        assert sel.sum() == T - 1
+        lo[sel] = hi[sel]
+        hi[sel] = np.minimum(np.array([rb[min(t + 1, Tmax - 1)] for t in range(1, T)]) + r, pl.N - 1)
+    return lo, hi
+
+
+def _backward(case, fwd, delta, dtype, mutant, mixed=None):
+    """packed backward pass in `dtype` from the float64 forward reference and CTC delta; `mixed`: a Rounding record (the
+    fp16-operand configuration: float64 is the model, float32 its noise estimate) or None (the reference's arithmetic)"""
+    p, pl, TL, NL, mx = case.params, case.plan, case.TL, case.NL, case.max_act
+    name, arg = mutant if mutant else (None, None)
+    m = _mutated(mixed, name, arg)
+    rb, nact, Tmax = pl.rowbase, pl.nact, pl.Tmax
+    cast = lambda a: np.ascontiguousarray(a, dtype=dtype)
+    if m is None:
+        rnd = rnd_delta = lambda a: a
+    else:
+        rnd = lambda a: cast(obrnn.round_bf16(a))
+        fn = {"bf16": obrnn.round_bf16, "trunc": trunc_bf16, "f16": obrnn.round_f16}[m.delta]
+        rnd_delta = (lambda a: cast(fn(a)))
+        if m.delta == "trunc":
+            rnd = rnd_delta
+    skip = m.skip if m is not None else None
+    op_b = lambda a, where: a if where == skip else rnd(a)
     W = [cast(w) for w in p["W"]]
     acts = [cast(a) for a in fwd["acts"]]
     hF, hB = fwd["hF"], fwd["hB"]
@@ -292,52 +369,72 @@ def _backward(case, fwd, delta, dtype, mutant):
     else:
         mF, mB = cast((hF > 0) & (hF < mx)), cast((hB > 0) & (hB < mx))
     dW, db = [None] * (NL + 1), [None] * (NL + 1)
-    dWf = dWb = None
+    dWf = dWb = dF = dB = None
+    shadows = {}
     d_in = cast(delta)
+    d16 = rnd_delta(d_in)                         # the one shadow every reader of d_in takes
+    op_a = lambda where: d_in if where == skip else d16
     for i in range(NL, -1, -1):
-        dW[i] = d_in @ acts[i].T
-        db[i] = d_in.sum(axis=1, keepdims=True)
+        dW[i] = op_a(("dW", i, "A")) @ op_b(acts[i], ("dW", i, "B")).T
+        db[i] = (d16 if m is None or m.db16 else d_in).sum(axis=1, keepdims=True)
         if i == 0:
             break
-        d_out = W[i].T @ d_in
+        d_out = rnd(W[i].T) @ op_a(("dgrad", i, "A"))
         if i == TL:
             WfT, WbT = cast(p["Wf"].T), cast(p["Wb"].T)
+            rec16 = m is not None and m.rec16
+            if rec16:
+                WfT, WbT = rnd(WfT), rnd(WbT)
+            read = rnd_delta if rec16 else (lambda a: a)            # the state as the next step reads it
+            store = rnd_delta if m is not None and m.state16 else None
             dF, dB = np.array(d_out), np.array(d_out)
             for u in range(Tmax - 1, -1, -1):
                 n = nact[u]
                 n1 = nact[u + 1] if u + 1 < Tmax else 0
-                if n1:
-                    dF[:, rb[u]:rb[u] + n1] += WfT @ dF[:, rb[u + 1]:rb[u + 1] + n1]
+                if n1 and not (name == "drop_bptt" and u == arg):   # mutant: no recurrent term at one step
+                    dF[:, rb[u]:rb[u] + n1] += WfT @ read(dF[:, rb[u + 1]:rb[u + 1] + n1])
                 dF[:, rb[u]:rb[u] + n] *= mF[:, rb[u]:rb[u] + n]
+                if store:
+                    dF[:, rb[u]:rb[u] + n] = store(dF[:, rb[u]:rb[u] + n])
             dB[:, :nact[0]] *= mB[:, :nact[0]]
+            if store:
+                dB[:, :nact[0]] = store(dB[:, :nact[0]])
             for t in range(1, Tmax):
                 n = nact[t]
-                dB[:, rb[t]:rb[t] + n] += WbT @ dB[:, rb[t - 1]:rb[t - 1] + n]
+                dB[:, rb[t]:rb[t] + n] += WbT @ read(dB[:, rb[t - 1]:rb[t - 1] + n])
                 dB[:, rb[t]:rb[t] + n] *= mB[:, rb[t]:rb[t] + n]
-            hi = np.concatenate([rb[t] + np.arange(nact[t]) for t in range(1, Tmax)] + [np.zeros(0, dtype=np.int64)])
-            lo = np.concatenate([rb[t - 1] + np.arange(nact[t]) for t in range(1, Tmax)] + [np.zeros(0, dtype=np.int64)])
-            hi, lo = hi.astype(np.int64), lo.astype(np.int64)
-            dWf = dF[:, hi] @ cast(hF[:, lo]).T
-            dWb = dB[:, lo] @ cast(hB[:, hi]).T
+                if store:
+                    dB[:, rb[t]:rb[t] + n] = store(dB[:, rb[t]:rb[t] + n])
+            lo, hi = pair_rows(pl, arg if name == "pair_shift" else None)
+            shadows["dF"], shadows["dB"] = rnd_delta(dF), rnd_delta(dB)
+            dWf = (dF if skip == ("dWf", "A") else shadows["dF"])[:, hi] @ rnd(cast(hF[:, lo])).T
+            dWb = (dB if skip == ("dWb", "A") else shadows["dB"])[:, lo] @ rnd(cast(hB[:, hi])).T
             d_out = dF + dB
         else:
             d_out = d_out * cast(fwd["acts"][i] > 0.0)
         d_in = d_out
-    return {"d1": d_in, "grads": {"W": dW, "b": db, "Wf": dWf, "Wb": dWb}}
+        d16 = rnd_delta(d_in)
+        shadows["d%d" % i] = d16
+    return {"d1": d_in, "dF": dF, "dB": dB, "shadows": shadows, "grads": {"W": dW, "b": db, "Wf": dWf, "Wb": dWb}}
 
 
-def reference(case, dtype=np.float64, backward=True, mutant=None):
+def reference(case, dtype=np.float64, backward=True, mutant=None, mixed=None):
     """-> dict, per utterance in the caller's order, (features, T) each: z, preF, preB, hF, hB, acts (list over layers
-    0..NL+1 of per-utterance lists), logits, d1; and costs, skips, grads (the SUM over the utterances, oracle layout).
-    The forward pass is float64 always (it is exact); dtype=np.float32 runs the backward part in float32."""
+    0..NL+1 of per-utterance lists), logits, d1, dF, dB (deltasFor / deltasBack); and costs, skips, grads (the SUM over the
+    utterances, oracle layout).  The forward pass is float64 always (it is exact); dtype=np.float32 runs the backward
+    part in float32.  mixed: a Rounding record -- the backward pass of the fp16-operand configuration; then also
+    shadows = {"dF", "dB", "d1", .. "d<NL>": per utterance}, the values of the 16-bit delta shadows."""
     pl = case.plan
     fwd = case.fwd if mutant is None else _forward(case, mutant)
     out = {k: _unpack(fwd[k], pl) for k in ("z", "preF", "preB", "hF", "hB", "logits")}
     out["acts"] = [_unpack(a, pl) for a in fwd["acts"]]
     if backward:
         costs, delta, skips = _ctc(case, fwd)
-        bw = _backward(case, fwd, delta, dtype, mutant)
-        out.update(costs=costs, skips=skips, d1=_unpack(bw["d1"], pl), grads=bw["grads"])
+        bw = _backward(case, fwd, delta, dtype, mutant, mixed)
+        out.update(costs=costs, skips=skips, d1=_unpack(bw["d1"], pl), dF=_unpack(bw["dF"], pl), dB=_unpack(bw["dB"], pl),
+                   grads=bw["grads"])
+        if mixed is not None:
+            out["shadows"] = {k: _unpack(v, pl) for k, v in bw["shadows"].items()}
     return out
 
 
@@ -386,6 +483,74 @@ def grad_tensors(grads):
     return out + [("dWf", grads["Wf"]), ("dWb", grads["Wb"])]
 
 
+# ------------------------------------------------------------------ the fp16-operand backward pass: statistics and bounds
+
+FLOOR = 2.0 ** -24           # a relative error cannot be asked to be smaller: the results are stored in fp32
+SHADOW_SHARE = 1e-3          # share of a bfloat16 delta shadow's elements that may differ from the float64 model's ...
+REF_SHADOW_SHARE = 2e-4      # ... and what the float32 model alone stays within on every f16 row (the CPU suite asserts it)
+REF_SEEDS = tuple(range(8))
+SHADOWS = ("dF", "dB", "d1", "d2")
+
+
+def mixed_stats(got, m64, max_act):
+    """every figure the fp16-operand backward check looks at.  got / m64: shaped like reference(..., mixed=) -- grads, dF,
+    dB and shadows[name] per utterance (the shadows as VALUES) -- m64 the float64 rounding model.  ->
+    fro:<tensor>   relative Frobenius error per gradient tensor
+    row:dF|dB|d1   largest per-frame relative error (d1: of the bfloat16 shadow against the model's shadow)
+    open:dF|dB     elements behind a closed (0, maxAct) mask that are not exactly zero
+    dirty:d1       frames of delta_1 that are zero in the model and not in got
+    share:<shadow> share of the shadow's elements whose value differs from the model's (-0.0 == 0.0), no frame left out"""
+    st = {}
+    for (name, g), (_, r) in zip(grad_tensors(got["grads"]), grad_tensors(m64["grads"])):
+        st["fro:" + name] = rel_fro(g, r)
+    for k, hk in (("dF", "hF"), ("dB", "hB")):
+        st["row:" + k] = row_errors(got[k], m64[k])[0]
+        st["open:" + k] = sum(int((np.asarray(g)[~((h > 0) & (h < max_act))] != 0).sum()) for g, h in zip(got[k], m64[hk]))
+    st["row:d1"], st["dirty:d1"] = row_errors(got["shadows"]["d1"], m64["shadows"]["d1"])
+    for k in SHADOWS:
+        pairs = [(np.asarray(g, dtype=np.float32), np.asarray(r, dtype=np.float32)) for g, r in zip(got["shadows"][k], m64["shadows"][k])]
+        assert all(g.shape == r.shape for g, r in pairs) and len(pairs) == len(m64["hF"])
+        st["share:" + k] = sum(int((g != r).sum()) for g, r in pairs) / float(sum(r.size for _, r in pairs))
+    return st
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_e_ref(H, B, NL, TL, Tmax, rec16):
+    """per statistic: the largest over seeds 0..7 of this shape of the float32-accumulating rounding model against the
+    float64-accumulating one (not floored).  Several seeds, because one rounding flip moves a figure and the device's
+    flips need not be NumPy's."""
+    worst = {}
+    for seed in REF_SEEDS:
+        case = make_case.__wrapped__(H, B, NL=NL, TL=TL, Tmax=Tmax, seed=seed)
+        mixed = Rounding(rec16)
+        st = mixed_stats(reference(case, np.float32, mixed=mixed), reference(case, mixed=mixed), case.max_act)
+        for k, v in st.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    return worst
+
+
+def mixed_violations(st, e_ref, margin):
+    """the rules of tests/test_gpu_recurrence_exact.py on mixed_stats' figures -> the list of those broken"""
+    out = []
+    for k, v in sorted(st.items()):
+        kind = k.split(":")[0]
+        if kind in ("fro", "row"):
+            bound = margin * max(e_ref[k], FLOOR)
+            if not v <= bound:
+                out.append("%s %.3g > %g x max(%.3g, 2^-24)" % (k, v, margin, e_ref[k]))
+        elif kind == "share":
+            if not v <= SHADOW_SHARE:
+                out.append("%s %.3g > %g" % (k, v, SHADOW_SHARE))
+        elif v != 0:
+            out.append("%s %d != 0" % (k, v))
+    return out
+
+
+def rounding_of(c):
+    """the Rounding record of a GPU_CASES row (None: not the fp16-operand configuration)"""
+    return Rounding(rec16=c.path == "mh") if c.mode == "f16" else None
+
+
 # ------------------------------------------------------------------ the GPU matrix
 
 def _c(path, H, B, variant="0", mode="f32", NL=2, TL=1, Tmax=None, rec_path=(1, 1, 0), seed=0):
@@ -407,6 +572,14 @@ GPU_CASES = (
     + [_c("mh", H, B, mode="f16") for H in (512, 1824) for B in (6, 16)]
     # fp16 operands around an fp32 recurrence: sentinel kernel at 2, two-chain flag kernel at 24
     + [_c("s4", 512, 2, mode="f16"), _c("q2", 512, 24, mode="f16")]
+    # fp16 operands, the rest of what a backward pass can meet: other chunk counts per wave of the 16-bit exchange kernel
+    # and an odd minibatch; the single-chain flag kernel at 5; 40 utterances (one launch: no cut with 16-bit operands); the
+    # per-step fallback; a ReLU layer below the temporal one (its delta GEMM masks by the sign of a 16-bit shadow)
+    + [_c("mh", 1024, 12, mode="f16"), _c("mh", 2048, 9, mode="f16"), _c("q1", 512, 5, mode="f16"),
+       _c("slab", 512, 40, mode="f16"), _c("fallback", 512, 7, variant="3", mode="f16", rec_path=(3, 3, 0)),
+       # (12 utterances, not the fp32 row's 5: with 11 000 elements per shadow three rounding flips of the float32 model
+       # would already be more than the 2e-4 the CPU suite holds it to)
+       _c("below-tl", 200, 12, NL=3, TL=2, mode="f16")]
     # 17..32 at the large layers: 16 units x both tiles of a direction per CU
     + [_c("t-ug1", H, B) for H in (1824, 2048) for B in (17, 24, 32)]
     # 17..32 at the small layers, and at the large one when asked for: two chains per CU

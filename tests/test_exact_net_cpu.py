@@ -6,7 +6,12 @@
   both boundaries, every 16 x 16 block of Wf / Wb occupied, no skip) hold for every entry of the GPU matrix;
 * mutants of the reference itself -- a dropped K chunk of one row block, a stale state, a backward direction started
   at the wrong frame, swapped rows, a non-strict mask, a ceiling off by 2^-20 -- are all reported by the very
-  comparison tests/test_gpu_recurrence_exact.py applies to the device's buffers."""
+  comparison tests/test_gpu_recurrence_exact.py applies to the device's buffers;
+* the rounding model of the fp16-operand backward pass (exact_net.Rounding) changes nothing when it is off, equals
+  oracle.brnn.Mixed utterance by utterance when it accumulates in float64, keeps its own float32 noise within what the
+  GPU suite's bounds assume on every f16 row of the matrix, and every wrong rounding point -- truncation, a recurrence
+  that rounds when it should not or the reverse, a 16-bit BPTT state, bias gradients of unrounded deltas, a dropped
+  BPTT step, float16 delta shadows, one unrounded GEMM operand, row pairs one frame late -- breaks one of those bounds."""
 import numpy as np
 import pytest
 
@@ -113,6 +118,130 @@ def test_forward_comparison_reports_every_mutant(H, B):
         assert differs == (n_rows > 0)
         if n_rows == 0:
             missed.append(mutant)
+    assert not missed, missed
+
+
+def _sum_grads(a, b):
+    return b if a is None else {"W": [x + y for x, y in zip(a["W"], b["W"])], "b": [x + y for x, y in zip(a["b"], b["b"])],
+                                "Wf": a["Wf"] + b["Wf"], "Wb": a["Wb"] + b["Wb"]}
+
+
+@pytest.mark.parametrize("H,B", [(96, 5), (512, 6)])
+def test_mixed_none_is_the_reference_of_before(H, B):
+    """the rounding model is an option: without it the same operations run on the same arrays, so the result is the
+    same bit for bit in both accumulation types (the identity stands where a rounding would) -- and it still equals the
+    unrounded oracle (test_reference_equals_oracle)"""
+    case = en.make_case(H, B)
+    for dt in (np.float64, np.float32):
+        a, b = en.reference(case, dt), en.reference(case, dt, mixed=None)
+        for (name, x), (_, y) in zip(en.grad_tensors(a["grads"]), en.grad_tensors(b["grads"])):
+            assert x.dtype == dt and y.dtype == dt
+            _same(x, y)
+        for k in ("d1", "dF", "dB"):
+            for x, y in zip(a[k], b[k]):
+                _same(x, y)
+        assert "shadows" not in a
+    # dF + dB is the delta entering the temporal layer's weight gradient: with TL = 1 that is d1
+    assert case.TL == 1
+    for d1, dF, dB in zip(a["d1"], a["dF"], a["dB"]):
+        _same(d1, dF + dB)
+
+
+@pytest.mark.parametrize("H,B", [(96, 5), (512, 6)])
+@pytest.mark.parametrize("rec", [True, False])
+def test_rounding_model_equals_oracle_mixed(H, B, rec):
+    """float64 accumulation: the batched rounding model is oracle.brnn's Mixed, utterance by utterance"""
+    case = en.make_case(H, B)
+    m64 = en.reference(case, mixed=en.Rounding(rec))
+    total = None
+    for b in range(B):
+        out = {}
+        c, g, s, _ = obrnn.cost_and_grad(case.params, case.datas[b], case.labs[b], case.TL, max_act=case.max_act,
+                                         mixed=obrnn.Mixed(rec=rec), cache_out=out)
+        assert not s and m64["costs"][b] == pytest.approx(c, rel=1e-12)        # the forward pass is exact either way
+        _same(m64["hF"][b], out["hF"])
+        _same(m64["hB"][b], out["hB"])
+        assert en.rel_fro(m64["d1"][b], out["d1"]) <= 1e-12
+        _same(m64["shadows"]["d1"][b], obrnn.round_bf16(m64["d1"][b]))
+        total = _sum_grads(total, g)
+    for (name, got), (_, want) in zip(en.grad_tensors(m64["grads"]), en.grad_tensors(total)):
+        assert en.rel_fro(got, want) <= 1e-12, name
+    # and it is not the unrounded reference: bfloat16 operands cost 1e-4 .. 5e-2 per tensor
+    ex = en.reference(case)
+    for (name, got), (_, want) in zip(en.grad_tensors(m64["grads"]), en.grad_tensors(ex["grads"])):
+        assert 1e-4 < en.rel_fro(got, want) < 5e-2, name
+
+
+def _f16_rows():
+    seen, rows = set(), []
+    for c in en.GPU_CASES:
+        key = (c.H, c.B, c.NL, c.TL, c.Tmax, c.path == "mh")
+        if c.mode == "f16" and key not in seen:
+            seen.add(key)
+            rows.append(c)
+    return rows
+
+
+@pytest.mark.parametrize("c", _f16_rows(), ids=lambda c: c.id)
+def test_rounding_model_conditions_on_the_f16_rows(c):
+    """what the GPU suite's bounds rest on, on the models alone: the float32-accumulating model differs from the float64
+    one (else 16 x e_ref would be the floor everywhere and the seeds pointless) wherever a sum is long or passes
+    through the recurrence -- dW1, dWf, dWb, deltasFor, deltasBack; the gradients above the temporal layer are sums of a
+    few hundred bfloat16 values of similar size, which fp32 may well add without any error, so 0 is allowed there and the
+    floor of 2^-24 holds the device -- and its bfloat16 shadows differ from the float64 model's in at most 2e-4 of their
+    elements, a fifth of what the device is allowed, on each of the eight seeds.  One flipped element of delta_1's shadow
+    is 2^-8 of itself and can be 4e-4 of dW1 (16 features: mh-H1024-B12, seed 2), so e_ref is not small everywhere; what
+    it must stay below is 5e-2 / 16, or the model's bound would be looser than the configuration's own 5e-2."""
+    assert 12 <= c.Tmax <= 16
+    e_ref = en.mixed_e_ref(c.H, c.B, c.NL, c.TL, c.Tmax, c.path == "mh")
+    for k in ("fro:dW1", "fro:dWf", "fro:dWb", "row:dF", "row:dB"):
+        assert e_ref[k] > 0, k
+    for k, v in e_ref.items():
+        kind = k.split(":")[0]
+        if kind == "share":
+            assert v <= en.REF_SHADOW_SHARE, (k, v)
+        elif kind in ("open", "dirty"):
+            assert v == 0, (k, v)
+        else:
+            assert v < 5e-2 / 16, (k, v)
+    assert en.rounding_of(c) == en.Rounding(c.path == "mh")
+
+
+def backward_mutants(case):
+    """(name, argument) of every backward mutant of the rounding model for this case"""
+    pl, NL, TL = case.plan, case.NL, case.TL
+    short = min((b for b in range(pl.B) if case.Ts[b] > 1), key=lambda b: (case.Ts[b], b))
+    out = [("trunc", None), ("rec_flip", None), ("state16", None), ("db_unrounded", None), ("f16_shadow", None),
+           ("pair_shift", short)]
+    out += [("drop_bptt", u) for u in (0, pl.Tmax // 2, pl.Tmax - 2)]
+    # one operand of one GEMM unrounded: the A (delta) operand of every kind of GEMM.  The B operands are left out,
+    # because on these networks they are no mutants: every value of the +-1 / power-of-two weights, the features, hF, hB
+    # and their sum is a bfloat16 value already (asserted); a ReLU layer's output is one unless it has an odd value
+    # above 256 (then its rounding is a mutant, and in the list)
+    for m in case.params["W"] + [case.params["Wf"], case.params["Wb"], case.fwd["acts"][0], case.fwd["acts"][TL],
+                                 case.fwd["hF"], case.fwd["hB"]]:
+        assert np.array_equal(obrnn.round_bf16(m), m)
+    out += [("unrounded", w) for w in [("dW", NL, "A"), ("dgrad", NL, "A"), ("dW", TL, "A"), ("dgrad", TL, "A"),
+                                       ("dW", 0, "A"), ("dWf", "A"), ("dWb", "A")]]
+    out += [("unrounded", ("dW", i, "B")) for i in range(1, NL + 1)
+            if not np.array_equal(obrnn.round_bf16(case.fwd["acts"][i]), case.fwd["acts"][i])]
+    return out
+
+
+@pytest.mark.parametrize("H,B,rec", [(512, 6, True), (512, 24, False), (96, 5, False)])
+def test_backward_comparison_reports_every_rounding_mutant(H, B, rec):
+    """every wrong rounding point, run with float32 accumulation like a device would, breaks one of the GPU suite's rules
+    at the GPU suite's bounds (exact_net.mixed_violations: per tensor and per frame 16 x e_ref, shadow shares 1e-3, zeros)
+    -- for a 16-bit-exchange shape, a fp32-recurrence shape and the generic layer size; the float32 model itself breaks
+    none.  A mutant no statistic sees is a failure of the statistics."""
+    case = en.make_case(H, B)
+    mixed = en.Rounding(rec)
+    e_ref = en.mixed_e_ref(H, B, case.NL, case.TL, case.dims[5], rec)
+    m64 = en.reference(case, mixed=mixed)
+    verdict = lambda mutant: en.mixed_violations(en.mixed_stats(en.reference(case, np.float32, mixed=mixed, mutant=mutant),
+                                                                m64, case.max_act), e_ref, 16.0)
+    assert verdict(None) == []
+    missed = [m for m in backward_mutants(case) if not verdict(m)]
     assert not missed, missed
 
 

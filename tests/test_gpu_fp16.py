@@ -4,7 +4,20 @@ SURVEY 8(d) cfg-5; NNet(..., fp16=True) / sctc_brnn_config.operand_dtype = SCTC_
 Numerics under test: the operands of every time-batched contraction (brnnet.py:140,196,204,
 227-230) and of the 6..16-utterance recurrent step (:148-152,215-224) are rounded to 16 bit --
 float16 in the forward pass, bfloat16 in the backward pass -- products exact, fp32 accumulation;
-master weights, stored activations, softmax, CTC (float64 lattices) unchanged.
+master weights, softmax, CTC (float64 lattices) unchanged.  A delta matrix is rounded once and every
+reader takes that copy: the weight gradient, the next delta GEMM, and the bias gradient, which is
+the column sum of the weight-gradient GEMM's delta operand (sums of bfloat16 deltas, not of the
+fp32 ones).  The BPTT state stays fp32; the 6..16-utterance kernel rounds the copy the next step
+reads.
+
+What is pinned where.  WHERE the backward pass rounds -- each point above, truncation against
+round-to-nearest, the bias gradients, a state kept in 16 bits -- is pinned in
+tests/test_gpu_recurrence_exact.py: on integer-grid networks the forward pass is exact, the masks
+are the reference's, and the device must agree with the float64 restatement of these roundings to
+fp32 accumulation accuracy (observed 1e-9 .. 4e-7 per tensor, up to 5e-5 where one or two elements
+of a 16-bit delta round the other way; bound 16 x the float32 restatement's own error, about 1e-6
+without such a flip; utterances of 12..16 frames).  HOW MUCH these roundings cost on real-valued
+data, over long utterances and at full size, is what this file holds, at the tolerances below.
 
 Two oracles: (i) oracle.brnn.Mixed restates exactly these roundings in float64 -- the GPU must
 agree with it to fp32-accumulation accuracy (cost 1e-4, gradients 2e-3; observed 7e-8 when only
