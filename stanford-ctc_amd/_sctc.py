@@ -282,7 +282,7 @@ def lib():
             raise ImportError("libsctc_hip.so ABI version mismatch")
         _lib = L
         # shared-device mode is not guessed here: the library finds out by itself how many processes use
-        # the physical GPU (marker files keyed by PCI bus id, csrc/recurrent.hip), and ranks of a process
+        # the physical GPU (marker files keyed by PCI bus id, csrc/device_share.h), and ranks of a process
         # group exchange their bus ids (resolve_shared_device, called by dist_sgd.DataParallel)
     return _lib
 

@@ -79,7 +79,8 @@ int launch_recurrent(const RecArgs& a, hipStream_t stream, int* path = nullptr);
 // clears the sticky error word (counters[2]): once per step, before its first recurrent launch
 int recurrent_clear_error(unsigned* counters, hipStream_t stream);
 // shared-device mode: persistent launches take an inter-process lease (flock on a per-device file)
-// and run synchronously.  Initial value: SCTC_SHARED_DEVICE in the environment.
+// and run synchronously.  Initial value: SCTC_SHARED_DEVICE in the environment.  The state and the guards
+// it switches are host code of their own: device_share.h (SharedMode).
 int recurrent_shared_device_mode();
 void recurrent_set_shared_device_mode(int on);
 

@@ -32,24 +32,14 @@
 // The K index inside a 16-chunk is permuted (k = 16c + 4*(lane>>4) + q for MFMA q)
 // identically for W and x, so both operands are 16-byte vector loads.
 #include <algorithm>
-#include <atomic>
 #include <map>
 #include <mutex>
-#include <utility>
-#include <vector>
-
-#include <dirent.h>
-#include <errno.h>
-#include <fcntl.h>
-#include <string.h>
 #include <string>
 #include <type_traits>
-#include <sys/stat.h>
-#include <sys/file.h>
-#include <time.h>
-#include <unistd.h>
+#include <utility>
 
 #include "common.h"
+#include "device_share.h"
 #include "recurrent.h"
 #include "xlane.h"
 
@@ -1763,263 +1753,40 @@ static RecKernel rec_kernel(const RecCandidate& c)
 
 // ------------------------------------------------------------------ co-residency guards
 //
-// Persistent kernels spin on other workgroups: every workgroup of the grid must be resident at
-// once.  Three things can break that, each with its own guard:
-//  (1) the grid does not fit the device at all (occupancy x CUs < grid): checked per (device,
-//      kernel) before the launch -> the per-step fallback runs instead;
-//  (2) ANOTHER PROCESS launches a persistent grid on the same device at the same time (two ranks
-//      sharing one GPU): both get part of the CUs and spin forever.  "Shared-device mode" takes an
-//      inter-process lease -- flock() on a per-device file in /dev/shm -- around every persistent
-//      launch: stream drained, lock, launch, wait, unlock.  It is on when SCTC_SHARED_DEVICE=1
-//      (the Python mirror sets it when the local ranks outnumber the visible devices) and turns
-//      itself on for the rest of the process the first time a launch times out; the normal
-//      one-rank-per-GPU path pays nothing;
-//  (3) another STREAM of this process does the same (one-utterance-per-stream): the in-process
-//      gate below admits a persistent launch only while the CUs of all persistent launches in
-//      flight on other streams, plus its own, fit the device; otherwise it first waits (on the
-//      host) for the oldest of them.
-// What still gets through (CU masks the runtime does not report, a foreign persistent kernel of
-// some other library) ends in the bounded spin -> SCTC_ERR_TIMEOUT -> the engine retries the step
-// on the fallback.
+// device_share.h has the guards and says what each is for; here is what they need from the GPU runtime.
 
-static std::atomic<int> g_shared_mode{-1};   // -1: not yet read from the environment
-static std::atomic<int> g_shared_hard{0};    // SCTC_SHARED_DEVICE was in the environment: no automatic switch
+int recurrent_shared_device_mode() { return device_share().mode.get(); }
+void recurrent_set_shared_device_mode(int on) { device_share().mode.set(on); }
 
-int recurrent_shared_device_mode()
+// device ordinal -> share_key of its PCI bus id: what the lease and the markers of a PHYSICAL device are named by
+static const std::string& device_share_key(int dev)
 {
-    int m = g_shared_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("SCTC_SHARED_DEVICE");
-        m = (e && atoi(e) != 0) ? 1 : 0;
-        if (e) g_shared_hard.store(1, std::memory_order_relaxed);
-        g_shared_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
-
-void recurrent_set_shared_device_mode(int on) { g_shared_mode.store(on ? 1 : 0, std::memory_order_relaxed); }
-
-namespace {
-
-static constexpr double LEASE_WAIT_S = 30.0;
-static double now_s()
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-struct DeviceLease {      // inter-process: one lock file per physical device
-    std::mutex mu;                       // serialises the threads of this process (flock is per open file)
-    std::map<int, int> fds;
-    int fd_for(int dev)
-    {
-        auto it = fds.find(dev);
-        if (it != fds.end()) return it->second;
-        char bus[64] = "unknown";
+    static std::mutex mu;
+    static std::map<int, std::string> keys;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = keys.find(dev);
+    if (it == keys.end()) {
+        char bus[64] = "";
         (void)hipDeviceGetPCIBusId(bus, sizeof(bus), dev);
-        for (char* c = bus; *c; ++c)
-            if (*c == ':' || *c == '.' || *c == '/') *c = '_';
-        char path[160];
-        int fd = -1;
-        const char* dirs[2] = {"/dev/shm", "/tmp"};
-        for (int k = 0; k < 2 && fd < 0; ++k) {
-            snprintf(path, sizeof(path), "%s/sctc_gpu_%s.lock", dirs[k], bus);
-            // the name is predictable and the directory world-writable: never follow a planted symlink,
-            // never touch the mode of anything but a regular file of our own
-            // the process umask is left alone (another thread creating a file at that moment would inherit a
-            // cleared one: ADVICE r04): the mode is widened on the DESCRIPTOR, and only of a regular file this
-            // user owns (O_NOFOLLOW: never through a planted symlink)
-            fd = open(path, O_CREAT | O_RDWR | O_CLOEXEC | O_NOFOLLOW, 0666);
-            if (fd >= 0) {
-                struct stat st;
-                if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); fd = -1; }
-                else if (st.st_uid == geteuid() && (st.st_mode & 0666) != 0666) (void)fchmod(fd, 0666);
-            }
-        }
-        fds[dev] = fd;
-        return fd;
+        it = keys.emplace(dev, share_key(bus)).first;
     }
+    return it->second;
+}
+
+struct HipEvents {      // PersistentGate's event operations
+    typedef hipEvent_t Event;
+    typedef hipStream_t Stream;
+    bool done(hipEvent_t ev)
+    {
+        const hipError_t q = hipEventQuery(ev);
+        if (q != hipSuccess && q != hipErrorNotReady) (void)hipGetLastError();
+        return q == hipSuccess;
+    }
+    int wait(hipEvent_t ev) { SCTC_HIP_TRY(hipEventSynchronize(ev)); return SCTC_OK; }
+    int create(hipEvent_t* ev) { SCTC_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming)); return SCTC_OK; }
+    int record(hipEvent_t ev, hipStream_t stream) { SCTC_HIP_TRY(hipEventRecord(ev, stream)); return SCTC_OK; }
 };
-DeviceLease g_lease;
-
-struct LeaseGuard {
-    int fd = -1;
-    bool locked = false;
-    explicit LeaseGuard(int dev)
-    {
-        g_lease.mu.lock();
-        fd = g_lease.fd_for(dev);
-        if (fd >= 0) {
-            // bounded: another user holding the lock for good must not hang this process with its
-            // mutex held -- after LEASE_WAIT_S the caller runs the step on the per-step fallback
-            // Polling with a growing back-off (200 us .. 5 ms) instead of a blocking flock: the wait must end, and a
-            // waiter that polls every 200 us re-acquires ahead of one that slept longer -- so every rank backs off the
-            // same way and a rank that has just held the lease yields once (below) before it asks again.
-            const double t0 = now_s();
-            useconds_t nap = 200;
-            for (;;) {
-                const int rc = flock(fd, LOCK_EX | LOCK_NB);
-                if (rc == 0) { locked = true; break; }
-                if (errno != EWOULDBLOCK && errno != EINTR) break;
-                if (now_s() - t0 > LEASE_WAIT_S) {
-                    // not silent: the step falls back to one launch per time step
-                    fprintf(stderr, "sctc: device lease not obtained within %.0f s (another process holds %s): this step "
-                                    "runs on the per-step recurrent kernels\n", LEASE_WAIT_S, "the GPU's persistent-launch lock");
-                    break;
-                }
-                usleep(nap);
-                if (nap < 5000) nap += nap / 2;
-            }
-        }
-    }
-    ~LeaseGuard()
-    {
-        if (locked) (void)flock(fd, LOCK_UN);
-        g_lease.mu.unlock();
-    }
-};
-
-// Who else uses this PHYSICAL device?  Every process that launches a persistent grid keeps an
-// exclusively flock'ed marker file /dev/shm/sctc_gpu_<pci-bus-id>.user.<pid> for its lifetime and touches it
-// at every persistent launch; counting the markers that are locked AND fresh tells how many processes are
-// launching persistent grids on the GPU right now,
-// whatever HIP_VISIBLE_DEVICES / LOCAL_WORLD_SIZE / device ordinals look like (round 3 guessed from
-// LOCAL_WORLD_SIZE > visible devices: wrong on an 8-GPU node whose launcher shows every rank one
-// device, and wrong the other way on a box that exports a global visibility mask).  More than one ->
-// shared-device mode switches itself on (one line on stderr).  Checked at persistent launches number
-// 1, 2, 4, ... 32 and every 32nd after that (a directory scan of /dev/shm, ~20 us) while the mode is
-// off; ranks that exchange their bus ids over a process group (dist_sgd.DataParallel) decide at once.
-static constexpr double USER_ACTIVE_S = 0.3;     // a marker untouched for this long belongs to an idle process (a trainer launches every few ms)
-static constexpr double MARKER_STALE_S = 2.0;   // an UNLOCKED marker older than this is a dead process's
-struct DeviceUsers {
-    std::mutex mu;
-    std::map<int, std::pair<int, std::string>> mine;    // device -> (held marker fd, marker prefix)
-    std::map<int, unsigned> launches;
-    static bool held_by_somebody(const char* path)
-    {
-        const int fd = open(path, O_RDWR | O_CLOEXEC | O_NOFOLLOW);
-        if (fd < 0) return false;
-        struct stat st;
-        bool held = false;
-        if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) {
-            if (flock(fd, LOCK_SH | LOCK_NB) != 0) {
-                // alive -- and ACTIVE: its owner touches the marker at every persistent launch; a process
-                // that merely still exists (a test driver waiting for its child, an idle notebook) is no
-                // reason to serialise launches
-                struct timespec now;
-                clock_gettime(CLOCK_REALTIME, &now);
-                held = errno == EWOULDBLOCK && (double)(now.tv_sec - st.st_mtim.tv_sec) + 1e-9 * (double)(now.tv_nsec - st.st_mtim.tv_nsec) < USER_ACTIVE_S;
-            } else {
-                // unlocked: its owner is gone -- or has created it a moment ago and not locked it yet (create and
-                // lock are two calls): only a marker that has been lying there for a while is removed
-                struct timespec now;
-                clock_gettime(CLOCK_REALTIME, &now);
-                if ((double)(now.tv_sec - st.st_mtim.tv_sec) > MARKER_STALE_S) (void)unlink(path);
-                (void)flock(fd, LOCK_UN);
-            }
-        }
-        close(fd);
-        return held;
-    }
-    // number of live processes (this one included) that registered for device `dev`; 0: no markers to be had
-    int count(int dev)
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        auto it = mine.find(dev);
-        if (it == mine.end()) {
-            char bus[64] = "unknown";
-            (void)hipDeviceGetPCIBusId(bus, sizeof(bus), dev);
-            for (char* c = bus; *c; ++c)
-                if (*c == ':' || *c == '.' || *c == '/') *c = '_';
-            std::string prefix = std::string("sctc_gpu_") + bus + ".user.";
-            it = mine.emplace(dev, std::make_pair(-1, prefix)).first;
-        }
-        if (it->second.first < 0) {
-            // (re)create the marker: a failed attempt -- or a marker a scanner removed between our open() and
-            // flock() -- is tried again at the next check instead of leaving this process invisible for good
-            const std::string path = "/dev/shm/" + it->second.second + std::to_string((long)getpid());
-            int fd = open(path.c_str(), O_CREAT | O_RDWR | O_CLOEXEC | O_NOFOLLOW, 0666);
-            struct stat st, on_disk;
-            if (fd >= 0 && (flock(fd, LOCK_EX | LOCK_NB) != 0 || fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) ||
-                            stat(path.c_str(), &on_disk) != 0 || on_disk.st_ino != st.st_ino)) {
-                close(fd);      // not lockable, or the name no longer leads to the file we hold
-                fd = -1;
-            }
-            if (fd >= 0 && st.st_uid == geteuid() && (st.st_mode & 0666) != 0666) (void)fchmod(fd, 0666);
-            it->second.first = fd;
-        }
-        if (it->second.first < 0) return 0;
-        int n = 1;
-        const std::string own = it->second.second + std::to_string((long)getpid());
-        if (DIR* d = opendir("/dev/shm")) {
-            while (struct dirent* e = readdir(d)) {
-                if (strncmp(e->d_name, it->second.second.c_str(), it->second.second.size()) != 0) continue;
-                if (own == e->d_name) continue;
-                if (held_by_somebody((std::string("/dev/shm/") + e->d_name).c_str())) ++n;
-            }
-            closedir(d);
-        }
-        return n;
-    }
-    bool due(int dev)
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        auto it = mine.find(dev);
-        if (it != mine.end() && it->second.first >= 0) (void)futimens(it->second.first, nullptr);   // "active now"
-        const unsigned k = ++launches[dev];
-        return k <= 32 ? (k & (k - 1)) == 0 : (k & 31) == 0;
-    }
-};
-DeviceUsers g_users;
-
-struct PersistentGate {   // in-process: persistent launches in flight, per device
-    struct Entry { hipEvent_t ev; hipStream_t stream; int cus; };
-    std::mutex mu;
-    std::map<int, std::vector<Entry>> inflight;
-    std::vector<hipEvent_t> pool;
-
-    // Waits (on the host) until `cus` more compute units' worth of persistent workgroups fit next to
-    // what other streams have in flight, then launches and registers the launch's event -- all under
-    // ONE lock: two host threads on different streams cannot both see an empty device and both
-    // launch a whole-device grid (check-then-act race of the round-3 admit() / launched() pair).
-    template <typename Launch>
-    int admit_and_launch(int dev, hipStream_t stream, int cus, int device_cus, Launch launch)
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        std::vector<Entry>& v = inflight[dev];
-        for (;;) {
-            int other = 0;
-            for (size_t i = 0; i < v.size();) {
-                const hipError_t q = hipEventQuery(v[i].ev);
-                if (q == hipSuccess) {
-                    pool.push_back(v[i].ev);
-                    v.erase(v.begin() + i);
-                    continue;
-                }
-                if (q != hipErrorNotReady) (void)hipGetLastError();
-                if (v[i].stream != stream) other += v[i].cus;   // same stream: serialised anyway
-                ++i;
-            }
-            if (other == 0 || other + cus <= device_cus) break;
-            for (size_t i = 0; i < v.size(); ++i)
-                if (v[i].stream != stream) {
-                    SCTC_HIP_TRY(hipEventSynchronize(v[i].ev));
-                    break;
-                }
-        }
-        SCTC_HIP_TRY(launch());
-        hipEvent_t ev;
-        if (!pool.empty()) { ev = pool.back(); pool.pop_back(); }
-        else SCTC_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        SCTC_HIP_TRY(hipEventRecord(ev, stream));
-        v.push_back(Entry{ev, stream, cus});
-        return SCTC_OK;
-    }
-};
-PersistentGate g_gate;
-
-}  // namespace
+static PersistentGate<HipEvents> g_gate;
 
 // The dynamic-LDS attribute is set once per (device, kernel) and the grid is checked against the
 // blocks per CU the kernel can have: its LDS share (these kernels are LDS-limited by construction,
@@ -2069,7 +1836,6 @@ struct LaunchCtx {
     int tcfg;       // SCTC_REC_TCFG
 };
 
-// launches a persistent grid if it can be co-resident (returns 1), else leaves it to the caller (0)
 static int read_error_word(const RecArgs& a, hipStream_t stream, unsigned* e)
 {
     *e = 0;
@@ -2078,6 +1844,8 @@ static int read_error_word(const RecArgs& a, hipStream_t stream, unsigned* e)
     return SCTC_OK;
 }
 
+// launches a persistent grid if it can be co-resident (*done), else leaves it to the caller: does it fit the device?
+// -> is the device shared (a launch that is due looks for other processes)? -> under the lease, or through the gate
 static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu, size_t sentinel_bytes,
                              const RecArgs& a, const LaunchCtx& cx, bool* done)
 {
@@ -2088,19 +1856,13 @@ static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu,
     const int need_cus = (grid + per_cu - 1) / per_cu;
     if (sentinel_bytes)   // sentinel-fill the exchange rows (both directions)
         SCTC_HIP_TRY(hipMemsetAsync(a.xbuf, 0xFF, sentinel_bytes, cx.stream));
-    if (!recurrent_shared_device_mode() && !g_shared_hard.load(std::memory_order_relaxed) && g_users.due(cx.dev)) {
-        const int n = g_users.count(cx.dev);
-        if (n > 1) {
-            recurrent_set_shared_device_mode(1);
-            fprintf(stderr, "sctc: %d processes run persistent kernels on this GPU: shared-device mode on "
-                            "(their launches take turns under /dev/shm/sctc_gpu_*.lock)\n", n);
-        }
-    }
-    if (recurrent_shared_device_mode()) {
+    DeviceShare& share = device_share();
+    const std::string& key = device_share_key(cx.dev);
+    if (share.shared_for_launch(key)) {
         // the lease is held exactly while the grid runs: nothing of ours queued in front of it,
         // nobody else's persistent grid next to it
         SCTC_HIP_TRY(hipStreamSynchronize(cx.stream));
-        LeaseGuard lease(cx.dev);
+        LeaseGuard lease(share.lease, key);
         if (!lease.locked) return SCTC_OK;            // no lock file to be had: per-step fallback
         hipLaunchKernelGGL(k, dim3(grid), dim3(REC_THREADS), smem, cx.stream, a);
         SCTC_HIP_TRY(hipGetLastError());
@@ -2115,9 +1877,10 @@ static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu,
                              "up waiting for its peers (%d workgroups not co-resident)", grid);
         return SCTC_OK;
     }
-    SCTC_TRY(g_gate.admit_and_launch(cx.dev, cx.stream, need_cus, cx.cus, [&]() {
+    SCTC_TRY(g_gate.admit_and_launch(cx.dev, cx.stream, need_cus, cx.cus, [&]() -> int {
         hipLaunchKernelGGL(k, dim3(grid), dim3(REC_THREADS), smem, cx.stream, a);
-        return hipGetLastError();
+        SCTC_HIP_TRY(hipGetLastError());
+        return SCTC_OK;
     }));
     *done = true;
     if (cx.path) *cx.path = REC_PATH_PERSISTENT;

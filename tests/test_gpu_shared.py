@@ -2,9 +2,10 @@
 
 The reference's per-step launches (ctc_fast/nnets/brnnet.py:148-152, :215-224) run on any GPU,
 busy or not.  The persistent kernels that replace them need every workgroup of a pass resident at
-once, so the library carries three guards (csrc/recurrent.hip "co-residency guards"): an
-inter-process device lease, a per-step non-persistent fallback, and an automatic re-run of a step
-whose persistent launch timed out.  These tests drive each of them on the one GPU of the box."""
+once, so the library carries three guards (csrc/device_share.h, called from launch_persistent in
+csrc/recurrent.hip): an inter-process device lease, a per-step non-persistent fallback, and an
+automatic re-run of a step whose persistent launch timed out.  These tests drive each of them on the
+one GPU of the box; tests/test_device_share_cpu.py checks the guards' host code without one."""
 import json
 import os
 import subprocess
