@@ -465,6 +465,44 @@ int sctc_ctc_align_batch(const sctc_align_config* cfg, const void* logprobs_dev,
                          int32_t* frame_label_dev, int32_t* span_dev, double* scores_dev, int32_t* status_dev,
                          void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- best-path decoding of a batch: ctc_fast.pyx:154-187 and new_decoder/decoder.pyx:79-100 -------------------
+ * Added without an ABI version bump (still 6): sctc_ctc_bestpath_batch, sctc_log_rows.
+ *
+ * Input: a packed batch [sum T][ld], float32 or float64 (probabilities or log-probabilities: only their order and
+ * their sum matter); utterance b has T_b[b] rows from row frame_off[b].
+ *   best[t]  the column of the FIRST maximum of row t: `v > bv` from -inf over columns 0..A-1, a row of only -inf
+ *            gives 0 -- exactly sctc_argmax_rows.  NaN is outside the contract, as it is there.
+ *   frame t emits best[t] iff (t == 0 or best[t] != best[t-1]) and best[t] is none of drop[0..n_drop).  The
+ *            comparison is on RAW neighbours: a dropped symbol still separates two runs of one symbol.
+ *            ctc_fast.pyx:168-187 is this with drop = {blank, 1, 2, 8}; decoder.pyx:90-98 with drop = {0}.
+ * Output: the k-th emitted label of utterance b at ids_dev[o_b + k], o_b = sum_{q<b} T_b[q] (the layout of the beam
+ * searches at nbest == 1); lens_dev[b] the number of labels; spans_dev[o_b + k] = (first, last) frame of the label's
+ * run of equal best, inclusive (last is the reference's `align`); scores_dev[b] = sum_t row_t[best[t]] in float64,
+ * summed in the kernel's order (bit-defined only where every order is exact).  T_b = 0: length 0, score 0.0. */
+typedef struct sctc_bestpath_config {
+    int32_t B, A, dtype;          /* utterances >= 0, alphabet >= 1, SCTC_F32 | SCTC_F64 */
+    int32_t n_drop;               /* 0..16 */
+    int32_t drop[16];             /* symbol ids that are never emitted (the blank, the reference's 1, 2, 8, ...) */
+    int64_t ld;                   /* row stride in elements, >= A */
+    const int32_t* T_b;           /* host [B], >= 0 */
+    const int64_t* frame_off;     /* host [B]: first row of utterance b */
+} sctc_bestpath_config;
+
+/* ids_dev int32 [sum T], lens_dev int32 [B], spans_dev int32 [sum T][2] or NULL, scores_dev double [B] or NULL.
+ * SCTC_ERR_ARG (no device needed): NULL config, ids or lens; B < 0; A < 1; ld < A; n_drop outside 0..16; a negative
+ * T_b or frame_off; a dtype other than the two.  B == 0 launches nothing.  One launch, one workgroup per utterance;
+ * allocates no device memory; the utterance descriptors go through the calling thread's pinned host buffer as those
+ * of sctc_edit_distance_batch do (same remark on stream capture).  SCTC_BESTPATH_MAP=lane|wave in the environment
+ * forces the row-to-lane mapping (tests, A/B runs); by default A <= 4096 takes a row per lane, larger A a row per wave. */
+int sctc_ctc_bestpath_batch(const sctc_bestpath_config* cfg, const void* rows_dev, int32_t* ids_dev, int32_t* lens_dev,
+                            int32_t* spans_dev, double* scores_dev, void* stream);
+
+/* logp = (float) log((double) p), element by element over [rows][A] with row stride ld (columns A..ld are not
+ * touched); in place (logp_dev == probs_dev) is allowed; p == 0 gives -inf.  What writeLikelihoods.py computes on
+ * the host, for probabilities that stay on the device.  SCTC_ERR_ARG: rows < 0, A < 1, ld < A, a NULL pointer with
+ * rows > 0. */
+int sctc_log_rows(const float* probs_dev, float* logp_dev, int64_t rows, int32_t A, int64_t ld, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

@@ -93,6 +93,16 @@ class AlignConfig(ctypes.Structure):
 ALIGN_TOTAL = 1
 ALIGN_MAX_U = 4095
 
+
+class BestPathConfig(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("A", ctypes.c_int32), ("dtype", ctypes.c_int32), ("n_drop", ctypes.c_int32),
+                ("drop", ctypes.c_int32 * 16), ("ld", ctypes.c_int64), ("T_b", c_i32p), ("frame_off", c_i64p)]
+
+
+BESTPATH_MAX_DROP = 16
+BESTPATH_FRAMES_PER_BLOCK = 256     # csrc/ctc_bestpath.hip: frames a workgroup takes at a time
+BESTPATH_LANE_MAX_A = 4096          # alphabets up to this take a row per lane, larger ones a row per wave
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -150,6 +160,8 @@ PROTOTYPES = {
     "sctc_ctc_align_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(AlignConfig), ctypes.POINTER(ctypes.c_size_t)]),
     "sctc_ctc_align_batch": (ctypes.c_int, [ctypes.POINTER(AlignConfig), vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t,
                                             vp]),
+    "sctc_ctc_bestpath_batch": (ctypes.c_int, [ctypes.POINTER(BestPathConfig), vp, vp, vp, vp, vp, vp]),
+    "sctc_log_rows": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),

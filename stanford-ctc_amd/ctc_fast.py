@@ -16,7 +16,9 @@ search decoder of ``ctc_fast/new_decoder/decoder.pyx`` batched over utterances:
 neural :class:`DecodeNNLM` or a recurrent :class:`DecodeRNNLM`); and scoring: :func:`edit_distance_batch` (the table and
 trace-back of ``ctc_fast/editDistance.py`` and ``swbd-utils/editDist.pyx`` for many pairs in
 one launch), :func:`nbest_oracle`, and the forced alignment :func:`align_batch` with
-:func:`score_sentences` (the ``align`` and ``refScore`` of ``decoder_utils.decode``).
+:func:`score_sentences` (the ``align`` and ``refScore`` of ``decoder_utils.decode``); and the
+best path of a whole batch in one launch, :func:`decode_best_path_batch`, with :func:`log_rows` and
+:func:`edit_distance_device` for data that stays on the device.
 
 There is no CPU fallback: without the HIP library or without a GPU the calls raise.
 """
@@ -177,6 +179,84 @@ def collapse_best_path(best_path, blank=0):
             hyp.append(b)
             align.append(i)
     return hyp, align
+
+
+def decode_best_path_batch(probs, lengths=None, blank=0, drop=(1, 2, 8), spans=False, scores=False, device=False):
+    """Best path decoding of a batch in one launch: :func:`decode_best_path` for every
+    utterance at once -- arg-max per frame, collapse of repeats, ``blank`` and the ids of ``drop`` never emitted
+    (the default is the reference's hard-coded 1, 2, 8 of ctc_fast.pyx:176-179; a dropped symbol still
+    separates two runs of one symbol).
+
+    probs: as for :func:`decode_beam_batch` -- a list of (A, T_b) float32/float64 arrays, or a torch device
+    tensor [sum T][A] (any row stride) with ``lengths``; probabilities or log-probabilities.  ``blank=None``
+    drops nothing but ``drop``.  Returns (hyps, aligns), lists of int32 arrays: the labels, and the last frame
+    of each label (what ``decode_best_path`` returns for one utterance).  ``spans=True``: int32 [U, 2] arrays
+    (first, last frame) in place of aligns.  ``scores=True``: a third value, float64 [B], the sum of the arg-max
+    entries.  ``device=True``: nothing is read back; returns the device tensors (ids int32 [sum T] with the
+    labels of utterance b from sum_{q<b} T_q, lens int32 [B], spans int32 [sum T, 2] or None, scores float64
+    [B] or None)."""
+    what = "decode_best_path_batch"
+    arrs, src, A, T_b, dt, dtype = _decode_inputs(probs, lengths, what)
+    B = len(T_b)
+    never = sorted(set(([] if blank is None else [int(blank)]) + [int(d) for d in drop]))
+    if len(never) > _sctc.BESTPATH_MAX_DROP:
+        raise ValueError("%s: %d symbols to drop, the limit is %d" % (what, len(never), _sctc.BESTPATH_MAX_DROP))
+    torch = _sctc.require_gpu()
+    ld = int(A)
+    if src is None:
+        host = np.concatenate([np.ascontiguousarray(p.T, dtype=dt) for p in arrs], axis=0) if sum(T_b) else \
+            np.zeros((1, A), dtype=dt)
+        dev = torch.from_numpy(host).cuda()
+    else:       # rows of a wider tensor are read in place (ld > A)
+        dev = src if src.stride(1) == 1 and src.stride(0) >= A else src.contiguous()
+        ld = int(dev.stride(0))
+    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(T_b)[:-1]]) if B else [], dtype=np.int64)
+    cfg = _sctc.BestPathConfig(B, int(A), dtype, len(never), (ctypes.c_int32 * 16)(*never), ld, _sctc.i32(Tb),
+                               _sctc.i64(off))
+    sum_T = int(Tb.sum())
+    want_spans = bool(spans) or not device
+    ids = torch.empty(max(1, sum_T), dtype=torch.int32, device=dev.device)
+    lens = torch.empty(max(1, B), dtype=torch.int32, device=dev.device)[:B]
+    span = torch.empty((max(1, sum_T), 2), dtype=torch.int32, device=dev.device) if want_spans else None
+    score = torch.empty(max(1, B), dtype=torch.float64, device=dev.device)[:B] if scores else None
+    rc = _sctc.lib().sctc_ctc_bestpath_batch(ctypes.byref(cfg), dev.data_ptr(), ids.data_ptr(), lens.data_ptr(),
+                                             span.data_ptr() if want_spans else None,
+                                             score.data_ptr() if scores else None, _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    if device:
+        return ids, lens, span, score
+    lens_h = lens.cpu().numpy()
+    ids_h, span_h = ids.cpu().numpy(), span.cpu().numpy()
+    hyps = [ids_h[o:o + n].copy() for o, n in zip(off, lens_h)]
+    if spans:
+        second = [span_h[o:o + n].copy() for o, n in zip(off, lens_h)]
+    else:
+        second = [span_h[o:o + n, 1].copy() for o, n in zip(off, lens_h)]
+    if scores:
+        return hyps, second, score.cpu().numpy()
+    return hyps, second
+
+
+def log_rows(probs_dev, out=None):
+    """``(float) log((double) p)`` of a float32 device tensor [rows][A] (any row stride), element by element
+    on the device (``sctc_log_rows``): what ``writeLikelihoods.py`` computes on the host.  ``out`` may be the
+    input itself (in place); default: a new tensor.  p == 0 gives -inf."""
+    torch = _sctc.require_gpu()
+    if not (isinstance(probs_dev, torch.Tensor) and probs_dev.is_cuda and probs_dev.dtype == torch.float32
+            and probs_dev.dim() == 2 and (probs_dev.shape[1] == 0 or probs_dev.stride(1) == 1)
+            and probs_dev.stride(0) >= probs_dev.shape[1]):
+        raise ValueError("log_rows: a float32 [rows][A] device tensor with unit column stride expected")
+    if out is None:
+        out = torch.empty_strided(probs_dev.shape, probs_dev.stride(), dtype=torch.float32, device=probs_dev.device)
+    if tuple(out.shape) != tuple(probs_dev.shape) or out.stride() != probs_dev.stride() or out.dtype != torch.float32:
+        raise ValueError("log_rows: out must have the input's shape, strides and dtype")
+    rows, A = int(probs_dev.shape[0]), int(probs_dev.shape[1])
+    if rows and A:
+        rc = _sctc.lib().sctc_log_rows(probs_dev.data_ptr(), out.data_ptr(), rows, A, int(probs_dev.stride(0)),
+                                       _sctc.current_stream_ptr())
+        _sctc.check(rc, "log_rows")
+    return out
 
 
 class _DeviceHandle(object):
@@ -428,8 +508,9 @@ def _decode_inputs(logprobs, lengths, what):
     return arrs, None, A, T_b, dt, _sctc.F64 if dt == np.float64 else _sctc.F32
 
 
-def _decode_launch(cfg, bytes_fn, decode_fn, arrs, src, A, T_b, dt, nbest, what):
-    """workspace, upload, launch and read-back shared by the two beam searches"""
+def _decode_launch(cfg, bytes_fn, decode_fn, arrs, src, A, T_b, dt, nbest, what, device=False):
+    """workspace, upload, launch and read-back shared by the two beam searches; ``device``: no read-back, the
+    device tensors (ids, lens, scores) are returned as the search wrote them"""
     B = len(T_b)
     nbytes = bytes_fn(ctypes.byref(cfg))
     if nbytes == 0:
@@ -449,6 +530,8 @@ def _decode_launch(cfg, bytes_fn, decode_fn, arrs, src, A, T_b, dt, nbest, what)
     rc = decode_fn(ctypes.byref(cfg), dev.data_ptr(), ids.data_ptr(), lens.data_ptr(),
                    scores.data_ptr(), ws.data_ptr(), nbytes, _sctc.current_stream_ptr())
     _sctc.check(rc, what)
+    if device:
+        return ids, lens, scores
     ids, lens, scores = ids.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy()
     hyps = []
     base = 0
@@ -464,7 +547,7 @@ def _decode_launch(cfg, bytes_fn, decode_fn, arrs, src, A, T_b, dt, nbest, what)
     return hyps, scores.reshape(B, nbest)
 
 
-def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=None, nbest=1):
+def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=None, nbest=1, device=False):
     """CTC prefix beam search with an optional character LM, batched: the
     reference's ``BeamLMDecoder.decode`` (ctc_fast/new_decoder/decoder.pyx:136-193) for every
     utterance at once, one workgroup per utterance.
@@ -473,7 +556,9 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
     blank), or a torch device tensor [sum T][A] with ``lengths`` giving T_b.  lm: a
     :class:`DecodeLM`, a :class:`DecodeNNLM`, a :class:`DecodeRNNLM` (§4.10) or None (no LM term).  Returns (hyps, scores): with nbest == 1 a list
     of int32 symbol-id arrays and float64[B]; with nbest > 1 a list of lists and [B, nbest]
-    (entries beyond the beam: empty, -inf)."""
+    (entries beyond the beam: empty, -inf).  ``device=True``: nothing is read back; returns the device tensors
+    (ids int32 [nbest * sum T], rank n of utterance b from nbest * sum_{q<b} T_q + n * T_b; lens int32
+    [B * nbest]; scores float64 [B * nbest])."""
     arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, "decode_beam_batch")
     B = len(T_b)
     search = [(cfg, name) for kind, cfg, name in _BEAM_SEARCH if isinstance(lm, kind)]
@@ -492,7 +577,7 @@ def decode_beam_batch(logprobs, lengths=None, beam=40, alpha=1.0, beta=0.0, lm=N
     L = _sctc.lib()
     return _decode_launch(cfg, getattr(L, "sctc_ctc_%s_workspace_bytes" % name),
                           getattr(L, "sctc_ctc_%s_decode_batch" % name), arrs, src, A, T_b, dt, nbest,
-                          "decode_beam_batch")
+                          "decode_beam_batch", device=device)
 
 
 # decode_beam_batch by the type of its LM: the config class and the name of the entry points
@@ -573,14 +658,15 @@ class DecodeLexicon(_DeviceHandle):
         self.device_bytes = int(_sctc.lib().sctc_lexicon_bytes(h))
 
 
-def decode_lexicon_beam_batch(logprobs, lengths=None, lexicon=None, beam=40, alpha=1.0, beta=0.0, nbest=1):
+def decode_lexicon_beam_batch(logprobs, lengths=None, lexicon=None, beam=40, alpha=1.0, beta=0.0, nbest=1,
+                              device=False):
     """Lexicon-constrained CTC prefix beam search with a word-bigram LM, or with a word n-gram LM of
     order 2..5 when the lexicon was built with one (§4.6b), batched (DESIGN.md
     §4.6): the reference's ``decode_bg_lm`` (ctc_fast/decoder/bg_decoder.pyx:18-95) for every
     utterance at once, one workgroup per utterance.  Inputs and outputs as
     :func:`decode_beam_batch`; lexicon: a :class:`DecodeLexicon`.  A hypothesis spells lexicon
     words separated by the space symbol and may end inside a word; its score is
-    log(p_nb + p_b) + beta * (words finished)."""
+    log(p_nb + p_b) + beta * (words finished).  ``device=True`` as for :func:`decode_beam_batch`."""
     if not isinstance(lexicon, DecodeLexicon):
         raise ValueError("decode_lexicon_beam_batch: lexicon must be a ctc_fast.DecodeLexicon")
     arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, "decode_lexicon_beam_batch")
@@ -594,7 +680,7 @@ def decode_lexicon_beam_batch(logprobs, lengths=None, lexicon=None, beam=40, alp
                               _sctc.i64(off), float(alpha), float(beta), lexicon.handle)
     L = _sctc.lib()
     return _decode_launch(cfg, L.sctc_ctc_lexbeam_workspace_bytes, L.sctc_ctc_lexbeam_decode_batch, arrs, src, A,
-                          T_b, dt, nbest, "decode_lexicon_beam_batch")
+                          T_b, dt, nbest, "decode_lexicon_beam_batch", device=device)
 
 
 # ---- scoring: edit distance with error counts and alignments ----
@@ -683,6 +769,36 @@ def edit_distance_batch(a_seqs, b_seqs, ops=False, a_index=None):
     codes = got[24 * P:].view(np.int8)
     starts = np.concatenate([[0], np.cumsum(path_len)])
     return stats, [codes[starts[p]:starts[p] + lens[p]].copy() for p in range(P)]
+
+
+def edit_distance_device(a_dev, a_len, a_off, b_dev, b_len, b_off):
+    """:func:`edit_distance_batch` (counts only) for sequences that already lie on the device: pair p is
+    (a_dev[a_off[p] : a_off[p] + a_len[p]], b_dev[b_off[p] : b_off[p] + b_len[p]]).  a_dev, b_dev: contiguous
+    int32 device tensors; the lengths (0..8191) and offsets are host sequences, one entry per pair.  Returns the
+    stats as an int32 [P, 5] DEVICE tensor (distance, UP, LEFT, SUB, MATCH); nothing is read back."""
+    what = "edit_distance_device"
+    torch = _sctc.require_gpu()
+    for t in (a_dev, b_dev):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError("%s: contiguous int32 device tensors expected" % what)
+    a_len = np.ascontiguousarray(a_len, dtype=np.int32).reshape(-1)
+    b_len = np.ascontiguousarray(b_len, dtype=np.int32).reshape(-1)
+    a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+    b_off = np.ascontiguousarray(b_off, dtype=np.int64).reshape(-1)
+    P = a_len.shape[0]
+    if not (b_len.shape[0] == a_off.shape[0] == b_off.shape[0] == P):
+        raise ValueError("%s: lengths and offsets must have one entry per pair" % what)
+    for n, o, t in ((a_len, a_off, a_dev), (b_len, b_off, b_dev)):
+        if P and (n.min() < 0 or o.min() < 0 or int((o + n).max()) > t.numel()):
+            raise ValueError("%s: a sequence outside its tensor" % what)
+    stats = torch.empty((P, 5), dtype=torch.int32, device=a_dev.device)
+    if P == 0:
+        return stats
+    cfg = _sctc.EditConfig(P, 0, _sctc.i32(a_len), _sctc.i64(a_off), _sctc.i32(b_len), _sctc.i64(b_off))
+    rc = _sctc.lib().sctc_edit_distance_batch(ctypes.byref(cfg), a_dev.data_ptr(), b_dev.data_ptr(), stats.data_ptr(),
+                                              None, None, None, 0, _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    return stats
 
 
 # ---- forced alignment and sentence scoring (DESIGN.md §4.9) ----

@@ -82,6 +82,15 @@ class ArgmaxDecoder(DecoderBase):
                     hyp.append(self.int_char_map[int(pmInd)])
         return "".join(hyp), hyp_score
 
+    def decode_batch(self, probs_list):
+        """[(hyp, score)] of a list of (A, T) arrays, one launch (``ctc_fast.decode_best_path_batch`` with only
+        the blank dropped); the score is summed in float64 on the device, in the kernel's order"""
+        for p in probs_list:
+            if not isinstance(p, np.ndarray) or p.ndim != 2:
+                raise ValueError("decode_batch: (A, T) arrays expected")
+        ids, _, scores = ctc_fast.decode_best_path_batch(probs_list, blank=0, drop=(), scores=True)
+        return [(self._string(h), float(s)) for h, s in zip(ids, scores)]
+
 
 class BeamLMDecoder(DecoderBase):
     """Prefix beam search with a character LM (decoder.pyx:103-193), DESIGN.md §4.5."""

@@ -468,24 +468,97 @@ class NNet:
             c = c + self.regcost                    # added even when skipped (brnnet.py:178-186)
         return c, self.grad, bool(skip[0])
 
-    def forwardProbs(self, data_list):
-        """train=False path for a list of utterances -> list of float32 (outputDim, T) probs"""
+    def forwardDevice(self, data_list, log=False, out=None):
+        """The forward pass of a list of utterances (at most maxUtts) with the result left on the device:
+        (float32 tensor [sum T][outputDim] of softmax probabilities, utterance b from row sum_{q<b} T_q; T_b).
+        ``log=True``: natural-log probabilities instead (``sctc_log_rows`` in place: the float32 rounding of the
+        float64 logarithm, as ``writeLikelihoods.py`` takes it on the host).  ``out``: a contiguous float32
+        [sum T][outputDim] device tensor to write into.  Works on training models too: no gradient is touched."""
         torch = _sctc.require_gpu()
         if self._h is None:
             raise RuntimeError("initParams() / fromFile() first")
         T_b = [np.asarray(d).shape[1] for d in data_list]
         feats = self._stage(data_list)
         mb, keep = self._minibatch(feats, T_b, None)
-        out = torch.empty((int(sum(T_b)), self.outputDim), dtype=torch.float32, device="cuda")
+        rows = int(sum(T_b))
+        if out is None:
+            out = torch.empty((rows, self.outputDim), dtype=torch.float32, device="cuda")
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and tuple(out.shape) == (rows, self.outputDim)):
+            raise ValueError("forwardDevice: out must be a contiguous float32 [%d][%d] device tensor"
+                             % (rows, self.outputDim))
         rc = _sctc.lib().sctc_brnn_forward(self._h, ctypes.byref(mb), out.data_ptr(),
                                            _sctc.current_stream_ptr())
         _sctc.check(rc, "costAndGrad(train=False)")
+        if log and rows:
+            _sctc.check(_sctc.lib().sctc_log_rows(out.data_ptr(), out.data_ptr(), rows, self.outputDim,
+                                                  self.outputDim, _sctc.current_stream_ptr()), "forwardDevice")
+        return out, T_b
+
+    def forwardProbs(self, data_list):
+        """train=False path for a list of utterances -> list of float32 (outputDim, T) probs"""
+        out, T_b = self.forwardDevice(data_list)
         host = out.cpu().numpy()
         res, o = [], 0
         for T in T_b:
             res.append(np.asfortranarray(host[o:o + T].T))
             o += T
         return res
+
+    def evaluate(self, data_list, label_rows, decode="best", drop=(), lm=None, beam=40, alpha=1.0, beta=0.0,
+                 cost=True):
+        """CTC cost and error counts of a list of utterances against their transcripts, on the device from the
+        features to the counts: the forward pass in groups of maxUtts, the reference's CTC cost
+        and skip flag (``ctc_fast.ctc_loss_batch`` on the probabilities where they lie), a decoder, and the edit
+        distance of every transcript against its hypothesis.
+
+        decode: "best" -- the best path with the blank (0) and the ids of ``drop`` never emitted; "beam" -- the
+        prefix beam search over the log-probabilities with ``lm`` (any handle ``ctc_fast.decode_beam_batch``
+        accepts, or a ``ctc_fast.DecodeLexicon`` for the lexicon search), ``beam``, ``alpha``, ``beta``.
+        Returns {"stats": int32 [B, 5] in the order of ``editDistance.edit_distance(ref, hyp)`` (dist, ins, dels,
+        subs, corr), "hyps": list of int32 arrays, "cost": float64 [B], "skip": bool [B]} (cost and skip None with
+        ``cost=False``).  Only the hypothesis lengths, the counts, the costs, the flags and -- once, at the end --
+        the hypothesis ids are copied to the host.  The model's gradients are not touched."""
+        import ctc_fast
+        torch = _sctc.require_gpu()
+        if self._h is None:
+            raise RuntimeError("initParams() / fromFile() first")
+        if decode not in ("best", "beam"):
+            raise ValueError("evaluate: decode must be 'best' or 'beam'")
+        B = len(data_list)
+        if len(label_rows) != B:
+            raise ValueError("evaluate: %d transcripts for %d utterances" % (len(label_rows), B))
+        refs = [np.ascontiguousarray(np.asarray(l).reshape(-1), dtype=np.int32) for l in label_rows]
+        T_b = [int(np.asarray(d).shape[1]) for d in data_list]
+        off = np.concatenate([[0], np.cumsum(T_b)]).astype(np.int64)
+        A = self.outputDim
+        probs = torch.empty((int(off[-1]), A), dtype=torch.float32, device="cuda")
+        step = max(1, int(self.maxUtts))
+        for g in range(0, B, step):
+            self.forwardDevice(data_list[g:g + step], out=probs[int(off[g]):int(off[min(B, g + step)])])
+        costs = skips = None
+        if cost and B:
+            costs, _, skips = ctc_fast.ctc_loss_batch(probs, refs, blank=0, lengths=T_b)
+        if decode == "best":
+            ids, lens, _, _ = ctc_fast.decode_best_path_batch(probs, lengths=T_b, blank=0, drop=drop, device=True)
+        else:
+            ctc_fast.log_rows(probs, out=probs)
+            if isinstance(lm, ctc_fast.DecodeLexicon):
+                ids, lens, _ = ctc_fast.decode_lexicon_beam_batch(probs, lengths=T_b, lexicon=lm, beam=beam,
+                                                                  alpha=alpha, beta=beta, device=True)
+            else:
+                ids, lens, _ = ctc_fast.decode_beam_batch(probs, lengths=T_b, beam=beam, alpha=alpha, beta=beta,
+                                                          lm=lm, device=True)
+        lens_h = lens.cpu().numpy()[:B]
+        U_b = np.array([r.shape[0] for r in refs], dtype=np.int32)
+        ref_off = np.concatenate([[0], np.cumsum(U_b)]).astype(np.int64)
+        ref_dev = torch.from_numpy(np.concatenate(refs + [np.zeros(1, dtype=np.int32)])).cuda()
+        stats = ctc_fast.edit_distance_device(ref_dev, U_b, ref_off[:B], ids, lens_h, off[:B])
+        ids_h = ids.cpu().numpy()
+        return {"stats": stats.cpu().numpy(),
+                "hyps": [ids_h[o:o + n].copy() for o, n in zip(off[:B], lens_h)],
+                "cost": costs.cpu().numpy() if costs is not None else None,
+                "skip": skips.cpu().numpy().astype(bool) if skips is not None else None}
 
     def updateParams(self, scale, update):
         """w += scale*dw, b += scale*db for every pair (brnnet.py:251-256).  When `update`

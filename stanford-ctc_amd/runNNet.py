@@ -15,6 +15,13 @@ resume from ``epoch``/``num_files``/``params.pk`` with the learning rate re-deri
 Site-specific pieces of the reference (``run_cfg.py`` paths, git revision, the SCAIL output
 directory of test mode) are replaced by ``--outputDir`` / ``--likDir``.  ``--minibatch`` and
 torch.distributed data parallelism are the extensions of sgd.py.
+
+Scoring (the reference's ``# TODO Hook up with runDecode to do CER and WER computation``, runNNet.py:239;
+DESIGN.md §4.11), all of it ``NNet.evaluate`` -- forward pass, CTC cost, best path and edit distance on the
+device: ``--test --score`` logs the summed CTC cost and the character error rate of every file and of all of
+them and writes ``<likDir>/cer.txt`` (``key dist ins dels subs ref_len`` per utterance); ``--devDir D
+--devFiles N [--devAlisDir]`` evaluates shards 1..N of D with the current weights at the end of every epoch
+(rank 0), logs ``dev cost ... CER ...`` and appends ``epoch cost CER`` to ``<run>/dev_cer``.
 """
 import argparse
 import json
@@ -42,6 +49,10 @@ def build_parser():
     p.add_argument("--test", action="store_true")
     p.add_argument("--outputDir", default=None, help="run directory (default: runs/<time>)")
     p.add_argument("--likDir", default=None, help="test mode: where the log-likelihoods go")
+    p.add_argument("--score", action="store_true", help="test mode: also CTC cost and CER (cer.txt)")
+    p.add_argument("--devDir", default=None, help="training: shards evaluated after every epoch")
+    p.add_argument("--devFiles", type=int, default=0)
+    p.add_argument("--devAlisDir", default=None)
     # architecture
     p.add_argument("--layerSize", type=int, default=1824)
     p.add_argument("--numLayers", type=int, default=5)
@@ -86,6 +97,43 @@ def _bcast(obj, world):
     return box[0]
 
 
+def score_shard(nn, loader, fn, logger=None):
+    """``NNet.evaluate`` (best path, only the blank dropped) over shard ``fn`` of ``loader``: (keys, stats int32
+    [n, 5], ref_len [n], cost [n], skip [n]).  Utterances beyond the model's frame capacity are left out, as the
+    trainer leaves them out (sgd.py)."""
+    data_dict, alis, keys, sizes = loader.loadDataFileDict(fn)
+    keep = [k for k in keys if data_dict[k].shape[1] <= nn.maxBatch]
+    if logger is not None and len(keep) < len(keys):
+        logger.info("File %d: %d utterances longer than %d frames left out" % (fn, len(keys) - len(keep), nn.maxBatch))
+    labels = [np.array(alis[k], dtype=np.int32) for k in keep]
+    res = nn.evaluate([data_dict[k] for k in keep], labels, decode="best", drop=())
+    ref_len = np.array([len(l) for l in labels], dtype=np.int64)
+    return keep, res["stats"], ref_len, res["cost"], res["skip"]
+
+
+def _cost_sum(cost, skip):
+    """the cost of the utterances that the trainer would not skip"""
+    ok = ~np.asarray(skip, dtype=bool) & np.isfinite(cost)
+    return float(np.asarray(cost)[ok].sum())
+
+
+def dev_eval(nn, o, epoch, logger, output_dir):
+    """dev-set CTC cost and CER with the current weights; one line appended to <run>/dev_cer"""
+    loader = dl.DataLoader(o.devDir, o.rawDim, o.inputDim, o.devAlisDir or o.devDir)
+    dist = refs = 0
+    cost = 0.0
+    for i in range(1, o.devFiles + 1):
+        _, stats, ref_len, c, skip = score_shard(nn, loader, i, logger)
+        dist += int(stats[:, 0].sum())
+        refs += int(ref_len.sum())
+        cost += _cost_sum(c, skip)
+    cer = dist / float(max(1, refs))
+    logger.info("dev cost %f CER %f (epoch %d, %d errors in %d labels)" % (cost, cer, epoch, dist, refs))
+    with open(os.path.join(output_dir, "dev_cer"), "a") as f:
+        f.write("%d %r %r\n" % (epoch, cost, cer))
+    return cost, cer
+
+
 def run(args=None):
     opts = build_parser().parse_args(args)
     # data-parallel extension (SURVEY 8(e)): under `python -m torch.distributed.run --nproc-per-node N
@@ -107,7 +155,7 @@ def run(args=None):
     if opts.cfg_file:
         with open(opts.cfg_file) as f:
             cfg = json.load(f)
-        for k in ("test", "startFile", "likDir"):
+        for k in ("test", "startFile", "likDir", "score"):
             cfg[k] = getattr(opts, k)
         if opts.test:                      # runNNet.py:96-99: test data comes from the command line
             cfg["dataDir"], cfg["numFiles"] = opts.dataDir, opts.numFiles
@@ -125,6 +173,8 @@ def run(args=None):
     cfg["host"], cfg["pid"] = socket.gethostname(), os.getpid()
     cfg.setdefault("reg", 0.0)
     cfg.setdefault("minibatch", 1)
+    for k, v in (("score", False), ("devDir", None), ("devFiles", 0), ("devAlisDir", None)):
+        cfg.setdefault(k, v)
     o = argparse.Namespace(**cfg)
 
     master = rank == 0
@@ -204,6 +254,8 @@ def run(args=None):
             with open(o.out_file + ".epoch{0:02}".format(k), "wb") as fid:
                 opt.toFile(fid)
                 nn.toFile(fid)
+            if o.devDir and o.devFiles > 0:
+                dev_eval(nn, o, k, logger, output_dir)
         opt.alpha = opt.alpha / o.anneal
     if master:
         _write(os.path.join(output_dir, "sentinel"), "")   # run complete (run_utils.touch_file)
@@ -225,6 +277,18 @@ def test(o, logger):
     for i in range(o.startFile, o.numFiles + 1):
         logger.info("Running file %d" % i)
         writeLogLikes(loader, nn, i, out_dir, writePickle=True)
+    if o.score:
+        dist = refs = 0
+        cost = 0.0
+        with open(os.path.join(out_dir, "cer.txt"), "w") as f:
+            for i in range(o.startFile, o.numFiles + 1):
+                keys, stats, ref_len, c, skip = score_shard(nn, loader, i, logger)
+                for k, st, n in zip(keys, stats, ref_len):
+                    f.write("%s %d %d %d %d %d\n" % (k, st[0], st[1], st[2], st[3], n))
+                d, r, cs = int(stats[:, 0].sum()), int(ref_len.sum()), _cost_sum(c, skip)
+                logger.info("File %d cost %f CER %f" % (i, cs, d / float(max(1, r))))
+                dist, refs, cost = dist + d, refs + r, cost + cs
+        logger.info("Total cost %f CER %f (%d errors in %d labels)" % (cost, dist / float(max(1, refs)), dist, refs))
     return out_dir
 
 
