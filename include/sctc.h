@@ -503,6 +503,62 @@ int sctc_ctc_bestpath_batch(const sctc_bestpath_config* cfg, const void* rows_de
  * rows > 0. */
 int sctc_log_rows(const float* probs_dev, float* logp_dev, int64_t rows, int32_t A, int64_t ld, void* stream);
 
+/* ---- LM scores of label sequences and n-best rescoring: the second pass (ctc_fast/clm/clm_pp.py, the refScore of
+ * decoder_utils.decode) -----
+ * Added without an ABI version bump (still 6): sctc_lm_score_workspace_bytes, sctc_lm_score_batch,
+ * sctc_nbest_rank_batch. */
+
+#define SCTC_LM_NGRAM 0   /* lm is an sctc_lm_t */
+#define SCTC_LM_NN 1      /* an sctc_nnlm_t */
+#define SCTC_LM_RNN 2     /* an sctc_rnnlm_t */
+
+/* N sequences of CTC symbol ids on the device: sequence n is l[0..U) = labels_dev[label_off[n] .. + U_b[n]); offsets
+ * may repeat and may point into the ids of a beam search in place.  Term i of a sequence is log10 P_LM(l_i | <s>,
+ * l_0 .. l_{i-1}) over the LM ids sym_word[l_.]: the float32 value that the beam search of that LM adds for the
+ * extension (the same rnnlm_tile / nnlm_tile call, the same table probe and float32 additions). */
+typedef struct sctc_lm_score_config {
+    int32_t N;                  /* sequences, >= 0 */
+    int32_t A;                  /* symbols incl. the blank 0, 1..256 */
+    int32_t lm_kind;            /* SCTC_LM_NGRAM | SCTC_LM_NN | SCTC_LM_RNN */
+    int32_t reserved;           /* 0 */
+    const void* lm;             /* the handle of that kind */
+    const int32_t* sym_word;    /* host [A]: LM id of symbols 1..A-1 (n-gram: 1..255; neural: 0..V-1) */
+    const int32_t* U_b;         /* host [N], 0..8191 */
+    const int64_t* label_off;   /* host [N], >= 0 */
+} sctc_lm_score_config;
+
+/* *bytes: device workspace of the call: 24 bytes a sequence, the symbol map, for the recurrent LM 16 bytes per tile of
+ * 32 sequences, sum U float32 when `without_terms` (the call gets terms_dev == NULL), and the scratch of at most 512
+ * resident tiles of a neural LM; every slice rounded up to 256 bytes (csrc/lm_score_plan.h). */
+int sctc_lm_score_workspace_bytes(const sctc_lm_score_config* cfg, int32_t without_terms, size_t* bytes);
+
+/* terms_dev float32 [sum U] or NULL: the terms of sequence n from sum_{q<n} U_b[q].  sums_dev double [N]: the float64
+ * sum of the sequence's float32 terms, added in position order; no end-of-sentence term; U = 0 gives 0.0.
+ * status_dev int32 [N]: 0, or 2 for a sequence with a label outside [0, A) or equal to 0 (the blank has no LM id):
+ * sum -inf, its terms are not written, nothing outside the tables is read.
+ * SCTC_ERR_ARG (no device needed): NULL config, handle, arrays or outputs, N < 0, A outside 1..256, an unknown
+ * lm_kind, a length outside 0..8191, a negative offset, an LM id outside the LM's range; SCTC_ERR_WORKSPACE:
+ * workspace too small.  N == 0 launches nothing.  Allocates no device memory; the descriptors go through the calling
+ * thread's pinned host buffer into the workspace (same remark on stream capture as sctc_edit_distance_batch). */
+int sctc_lm_score_batch(const sctc_lm_score_config* cfg, const int32_t* labels_dev, float* terms_dev, double* sums_dev,
+                        int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Combine and rank B utterances x K hypotheses (K <= 256), pair (b, k) at b * K + k: scores_dev [B * K][2] and
+ * status_dev [B * K] of ONE sctc_ctc_align_batch call with SCTC_ALIGN_TOTAL over the pairs, lm_sums_dev [B * K] of
+ * sctc_lm_score_batch (NULL: no LM term, the sum counts as 0.0), U_b host [B * K] the lengths, K_b host [B]: the
+ * first K_b[b] ranks of utterance b are real hypotheses.  first_scores_dev (double [B * K] or NULL): the first
+ * pass's own scores; a rank at -inf there (the searches fill the ranks beyond the beam so) and every rank after it
+ * is not real either.
+ *   rescored_dev double [B][K]: (total + alpha * lm) + beta * U in float64, no contraction, for a real hypothesis
+ *                with align status 0; otherwise -inf.
+ *   order_dev int32 [B][K]: the hypothesis indices by descending rescored value, ties to the lower first-pass rank;
+ *                the ranks that are not real come last, in their original order.
+ * SCTC_ERR_ARG (no device needed): B < 0, K outside 1..256, NULL arrays, K_b outside [0, K], a negative length.
+ * B == 0 launches nothing.  One wave per utterance; the lengths go through the calling thread's pinned host buffer. */
+int sctc_nbest_rank_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_t* U_b, double alpha, double beta,
+                          const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
+                          const double* first_scores_dev, double* rescored_dev, int32_t* order_dev, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

@@ -103,6 +103,19 @@ BESTPATH_MAX_DROP = 16
 BESTPATH_FRAMES_PER_BLOCK = 256     # csrc/ctc_bestpath.hip: frames a workgroup takes at a time
 BESTPATH_LANE_MAX_A = 4096          # alphabets up to this take a row per lane, larger ones a row per wave
 
+
+
+class LmScoreConfig(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("A", ctypes.c_int32), ("lm_kind", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("lm", vp), ("sym_word", c_i32p), ("U_b", c_i32p), ("label_off", c_i64p)]
+
+
+LM_NGRAM, LM_NN, LM_RNN = 0, 1, 2
+LM_SCORE_MAX_U = 8191
+LM_SCORE_TILE = 32          # csrc/lm_score_plan.h: sequences (recurrent LM) or positions (window LM) per tile
+LM_SCORE_RESIDENT = 512     # resident tiles of a neural LM, each with its own scratch
+NBEST_MAX_K = 256
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -162,6 +175,11 @@ PROTOTYPES = {
                                             vp]),
     "sctc_ctc_bestpath_batch": (ctypes.c_int, [ctypes.POINTER(BestPathConfig), vp, vp, vp, vp, vp, vp]),
     "sctc_log_rows": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, vp]),
+    "sctc_lm_score_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(LmScoreConfig), ctypes.c_int32,
+                                                     ctypes.POINTER(ctypes.c_size_t)]),
+    "sctc_lm_score_batch": (ctypes.c_int, [ctypes.POINTER(LmScoreConfig), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "sctc_nbest_rank_batch": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p, ctypes.c_double,
+                                             ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),

@@ -933,6 +933,217 @@ def score_sentences(logprobs, seqs, lengths=None, lm=None, alpha=1.0, beta=0.0):
     return score
 
 
+# ---- LM scores on the device and n-best rescoring ----
+
+def _lm_kind(lm, what):
+    for kind, cls in ((_sctc.LM_NGRAM, DecodeLM), (_sctc.LM_NN, DecodeNNLM), (_sctc.LM_RNN, DecodeRNNLM)):
+        if isinstance(lm, cls):
+            return kind
+    raise ValueError("%s: lm must be a ctc_fast.DecodeLM, a ctc_fast.DecodeNNLM or a ctc_fast.DecodeRNNLM" % what)
+
+
+def _lm_score_launch(lm, sym_words, labels_dev, U_b, loff, want_terms, what):
+    """sctc_lm_score_batch on device labels: (sums float64 [N], terms float32 [sum U] or None, status int32 [N]),
+    device tensors; the workspace is a torch allocation that lives until the stream has run past the call"""
+    torch = _sctc.require_gpu()
+    kind = _lm_kind(lm, what)
+    N = int(U_b.shape[0])
+    sw = np.ascontiguousarray(sym_words, dtype=np.int32)
+    cfg = _sctc.LmScoreConfig(N, int(sw.shape[0]), kind, 0, lm.handle, _sctc.i32(sw), _sctc.i32(U_b), _sctc.i64(loff))
+    L = _sctc.lib()
+    nbytes = ctypes.c_size_t(0)
+    _sctc.check(L.sctc_lm_score_workspace_bytes(ctypes.byref(cfg), 0 if want_terms else 1, ctypes.byref(nbytes)), what)
+    device = labels_dev.device
+    sums = torch.empty(N, dtype=torch.float64, device=device)
+    status = torch.empty(N, dtype=torch.int32, device=device)
+    terms = torch.empty(max(1, int(U_b.sum())), dtype=torch.float32, device=device) if want_terms else None
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=device)
+    rc = L.sctc_lm_score_batch(ctypes.byref(cfg), labels_dev.data_ptr(), terms.data_ptr() if want_terms else None,
+                               sums.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes.value,
+                               _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    return sums, (terms[:int(U_b.sum())] if want_terms else None), status
+
+
+def _score_seqs(seqs, what, max_len):
+    """(device labels int32, U_b int32 [N], label_off int64 [N]) of a list of symbol-id arrays, or of a
+    device triple (ids, U, offsets) that is read in place"""
+    torch = _sctc.require_gpu()
+    if isinstance(seqs, tuple) and len(seqs) == 3 and isinstance(seqs[0], torch.Tensor):
+        ids, U, offs = seqs
+        if not (ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()):
+            raise ValueError("%s: ids must be a contiguous int32 [n] tensor on the device" % what)
+        U_b = np.ascontiguousarray(U.cpu().numpy() if isinstance(U, torch.Tensor) else U, dtype=np.int32).reshape(-1)
+        loff = np.ascontiguousarray(offs.cpu().numpy() if isinstance(offs, torch.Tensor) else offs,
+                                    dtype=np.int64).reshape(-1)
+        if U_b.shape[0] != loff.shape[0]:
+            raise ValueError("%s: %d lengths for %d offsets" % (what, U_b.shape[0], loff.shape[0]))
+        if U_b.size and ((U_b < 0).any() or (loff < 0).any() or int((loff + U_b).max()) > ids.shape[0]):
+            raise ValueError("%s: a sequence lies outside the ids tensor" % what)
+        labels = ids
+    else:
+        labs = [_edit_seq(s, what) for s in seqs]
+        U_b = np.ascontiguousarray([s.shape[0] for s in labs], dtype=np.int32)
+        loff = np.ascontiguousarray(np.concatenate([[0], np.cumsum(U_b)[:-1]]) if len(labs) else [], dtype=np.int64)
+        labels = torch.from_numpy(np.concatenate(labs + [np.zeros(1, dtype=np.int32)])).cuda()
+    if U_b.size and int(U_b.max()) > max_len:
+        raise ValueError("%s: a sequence of %d labels, the limit is %d" % (what, int(U_b.max()), max_len))
+    return labels, U_b, loff
+
+
+def lm_score_batch(seqs, lm, terms=False, device=False):
+    """float64 [N]: sum_i log10 P_LM(l_i | <s>, l_<i) of every label row under ``lm`` (a :class:`DecodeLM`, a
+    :class:`DecodeNNLM` or a :class:`DecodeRNNLM`), computed on the device: what
+    :func:`lm_sentence_scores` returns, bit for bit, in a few launches for the whole batch.  No end-of-sentence
+    term.  ``seqs``: a list of CTC symbol-id sequences, or a device triple (ids int32 tensor, U, offsets) read in
+    place -- sequence n is ids[offsets[n] : offsets[n] + U[n]]; offsets may repeat.  A sequence with a symbol
+    outside 1..A-1 scores -inf.  ``terms=True``: returns (sums, terms), terms the float32 value of every position
+    (a list of arrays; with ``device=True`` one flat tensor, sequence n from sum(U[:n])).  ``device=True``:
+    nothing is read back, the results are device tensors."""
+    what = "lm_score_batch"
+    _lm_kind(lm, what)
+    labels, U_b, loff = _score_seqs(seqs, what, _sctc.LM_SCORE_MAX_U)
+    sums, tv, _ = _lm_score_launch(lm, lm.sym_words, labels, U_b, loff, bool(terms), what)
+    if device:
+        return (sums, tv) if terms else sums
+    sums = sums.cpu().numpy()
+    if not terms:
+        return sums
+    flat = tv.cpu().numpy()
+    cuts = np.concatenate([[0], np.cumsum(U_b)]).astype(np.int64)
+    return sums, [flat[cuts[n]:cuts[n + 1]].copy() for n in range(U_b.shape[0])]
+
+
+def lm_perplexity(seqs_of_lm_ids, lm, eos=True):
+    """(perplexity, bits_per_char, n_terms) of sentences given as sequences of LM ids under ``lm`` (a Decode*LM
+    handle): 10 ** (-sum of the log10 terms / n), the ``compute_pp`` of the reference's ctc_fast/clm/clm_pp.py.
+    Every sentence starts from ``<s>``; with ``eos`` its ``</s>`` term is included.  The LM's ids are scored
+    under the identity symbol map (A = V), whatever CTC alphabet the handle was made for; id 0 is the place of
+    the blank and cannot be scored (ValueError)."""
+    what = "lm_perplexity"
+    kind = _lm_kind(lm, what)
+    if kind == _sctc.LM_NGRAM:
+        V, end = len(lm.arpa.words) + 1, lm.arpa.vocab.get("</s>")
+    else:
+        model = lm.nnlm if kind == _sctc.LM_NN else lm.rnnlm
+        V, end = model.V, model.eos
+    if eos and end is None:
+        raise ValueError("%s: the LM has no </s>" % what)
+    rows = []
+    for s in seqs_of_lm_ids:
+        r = [int(i) for i in s] + ([int(end)] if eos else [])
+        if any(not 1 <= i < V for i in r):
+            raise ValueError("%s: an LM id outside 1..%d" % (what, V - 1))
+        rows.append(np.asarray(r, dtype=np.int32))
+    n = int(sum(r.shape[0] for r in rows))
+    if n == 0:
+        raise ValueError("%s: nothing to score" % what)
+    labels, U_b, loff = _score_seqs(rows, what, _sctc.LM_SCORE_MAX_U)
+    sums, _, _ = _lm_score_launch(lm, np.arange(V, dtype=np.int32), labels, U_b, loff, False, what)
+    mean = float(sums.cpu().numpy().sum()) / n
+    return 10.0 ** (-mean), -mean * np.log2(10.0), n
+
+
+def rescore_nbest(logprobs, hyps, lengths=None, lm=None, alpha=1.0, beta=0.0, device=False, scores=None, K_b=None):
+    """Second pass over n-best lists: every hypothesis gets the score that
+    :func:`score_sentences` gives it, log P_ctc(l) + alpha * sum_i log10 P_LM(l_i | <s>, l_<i) + beta * U with the
+    full CTC sum, and every utterance's hypotheses are ranked by it -- one forced-alignment launch, one LM-score
+    call and one rank launch for the whole batch.  ``lm=None`` ranks by log P_ctc(l) + beta * U.
+
+    logprobs / lengths: as for :func:`decode_beam_batch`.  hyps: the list of lists that
+    ``decode_beam_batch(..., nbest=K)`` returns, or the device tensors ``(ids, lens, scores)`` of
+    ``decode_beam_batch(..., device=True)``, used in place (only ``lens`` is read back).  The ranks beyond the
+    beam (first-pass score -inf) are no hypotheses: they are recognised by the first-pass ``scores`` ([B, K]; the
+    device route has them) or by ``K_b`` (int [B]: the leading ranks that are real), stay last and score -inf.
+    Returns (order int32 [B, K]: hypothesis indices by descending score, ties to the lower first-pass rank;
+    rescored float64 [B, K]: by first-pass rank, -inf where the hypothesis cannot be aligned); device tensors
+    with ``device=True``."""
+    what = "rescore_nbest"
+    arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, what)
+    B = len(T_b)
+    torch = _sctc.require_gpu()
+    if lm is not None:
+        _lm_kind(lm, what)
+        if lm.sym_words.shape[0] < A:
+            raise ValueError("%s: the LM maps %d symbols, the input has %d" % (what, lm.sym_words.shape[0], A))
+    Tb = np.ascontiguousarray(T_b, dtype=np.int32)
+    foff = np.concatenate([[0], np.cumsum(Tb)[:-1]]).astype(np.int64) if B else np.zeros(0, np.int64)
+    first = None
+    if isinstance(hyps, tuple) and len(hyps) == 3 and isinstance(hyps[0], torch.Tensor):
+        ids, lens, first = hyps
+        if lens.numel() % max(B, 1):
+            raise ValueError("%s: %d lengths for %d utterances" % (what, lens.numel(), B))
+        K = lens.numel() // max(B, 1)
+        U_b = np.ascontiguousarray(lens.cpu().numpy(), dtype=np.int32).reshape(-1)
+        loff = (K * foff[:, None] + np.arange(K, dtype=np.int64)[None, :] * Tb[:, None].astype(np.int64)).reshape(-1)
+        labels = ids
+        if U_b.size and int((loff + U_b).max()) > ids.shape[0]:
+            raise ValueError("%s: a hypothesis lies outside the ids tensor" % what)
+        first = first.reshape(-1).contiguous()
+    else:
+        if len(hyps) != B:
+            raise ValueError("%s: %d n-best lists for %d utterances" % (what, len(hyps), B))
+        K = len(hyps[0]) if B else 1
+        if any(len(row) != K for row in hyps):
+            raise ValueError("%s: every utterance must have the same number of hypotheses" % what)
+        labels, U_b, loff = _score_seqs([h for row in hyps for h in row], what, _sctc.ALIGN_MAX_U)
+        if scores is not None:
+            first = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)).cuda()
+            if first.numel() != B * K:
+                raise ValueError("%s: scores must be [B, K]" % what)
+    if not 1 <= K <= _sctc.NBEST_MAX_K:
+        raise ValueError("%s: %d hypotheses per utterance outside 1..%d" % (what, K, _sctc.NBEST_MAX_K))
+    if U_b.size and int(U_b.max()) > _sctc.ALIGN_MAX_U:
+        raise ValueError("%s: a hypothesis of %d labels, the limit is %d" % (what, int(U_b.max()), _sctc.ALIGN_MAX_U))
+    loff = np.ascontiguousarray(loff, dtype=np.int64)
+    Kb = np.full(B, K, dtype=np.int32) if K_b is None else np.ascontiguousarray(K_b, dtype=np.int32).reshape(-1)
+    if Kb.shape[0] != B:
+        raise ValueError("%s: K_b must be [B]" % what)
+    # ---- one forced-alignment launch over the B * K pairs: the K hypotheses of an utterance share its frames ----
+    ld = int(A)
+    if src is not None:
+        dev = src if src.stride(1) == 1 and A <= src.stride(0) < 2 ** 31 else src.contiguous()
+        ld = int(dev.stride(0))
+    else:
+        host = np.concatenate([np.ascontiguousarray(p.T, dtype=dt) for p in arrs], axis=0) if sum(T_b) else \
+            np.zeros((1, A), dtype=dt)
+        dev = torch.from_numpy(host).cuda()
+    labels = labels.to(dev.device)
+    P = B * K
+    T_p = np.ascontiguousarray(np.repeat(Tb, K), dtype=np.int32)
+    f_p = np.ascontiguousarray(np.repeat(foff, K), dtype=np.int64)
+    cfg = _sctc.AlignConfig(P, int(A), dtype, 0, ld, _sctc.ALIGN_TOTAL, _sctc.i32(T_p), _sctc.i64(f_p), _sctc.i32(U_b),
+                            _sctc.i64(loff))
+    L = _sctc.lib()
+    nbytes = ctypes.c_size_t(0)
+    _sctc.check(L.sctc_ctc_align_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)), what)
+    device_ = dev.device
+    a_scores = torch.empty((max(P, 1), 2), dtype=torch.float64, device=device_)
+    a_status = torch.empty(max(P, 1), dtype=torch.int32, device=device_)
+    # the alignments themselves are not wanted; hypotheses of one utterance write the same frame labels
+    junk = torch.empty(int(Tb.sum()) + 2 * int(U_b.sum()) + 2, dtype=torch.int32, device=device_)
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=device_)
+    rc = L.sctc_ctc_align_batch(ctypes.byref(cfg), dev.data_ptr(), labels.data_ptr(), junk.data_ptr(),
+                                junk.data_ptr() + 4 * int(Tb.sum()), a_scores.data_ptr(), a_status.data_ptr(),
+                                ws.data_ptr() if nbytes.value else None, nbytes.value, _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    # ---- one LM-score call ----
+    lm_sums = None
+    if lm is not None and P:
+        lm_sums, _, _ = _lm_score_launch(lm, lm.sym_words[:A], labels, U_b, loff, False, what)
+    # ---- one rank launch ----
+    rescored = torch.empty((B, K), dtype=torch.float64, device=device_)
+    order = torch.empty((B, K), dtype=torch.int32, device=device_)
+    rc = L.sctc_nbest_rank_batch(B, K, _sctc.i32(Kb), _sctc.i32(U_b), float(alpha), float(beta), a_scores.data_ptr(),
+                                 a_status.data_ptr(), lm_sums.data_ptr() if lm_sums is not None else None,
+                                 first.data_ptr() if first is not None else None, rescored.data_ptr(),
+                                 order.data_ptr(), _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    if device:
+        return order, rescored
+    return order.cpu().numpy(), rescored.cpu().numpy()
+
+
 def nbest_oracle(refs, nbest_hyps):
     """Oracle error of n-best lists: for utterance b the hypothesis of ``nbest_hyps[b]`` (the list
     that ``decode_beam_batch(..., nbest=k)`` returns for it) closest to ``refs[b]``.  An empty

@@ -126,9 +126,35 @@ class BeamLMDecoder(DecoderBase):
         (hyp, score), = self.decode_batch([probs], beam, alpha, beta)
         return hyp, score
 
-    def decode_batch(self, probs_list, beam=40, alpha=1.0, beta=0.0, nbest=1):
+    def _rescore_lm(self, lm, A):
+        """the device handle of a second-pass LM: a ctc_fast.Decode*LM as it is, a model or the path of one uploaded
+        once per alphabet"""
+        if isinstance(lm, (ctc_fast.DecodeLM, ctc_fast.DecodeNNLM, ctc_fast.DecodeRNNLM)):
+            return lm
+        if self.int_char_map is None:
+            raise ValueError("BeamLMDecoder: load_chars first")
+        key = ("rescore", lm if isinstance(lm, str) else id(lm), A)
+        if key not in self._dev:
+            import nn_lm
+            model = lm
+            if isinstance(lm, str):
+                model = nn_lm.load(lm) if lm.endswith(".npz") else arpa_lm.ArpaLM(lm)
+            cls = ctc_fast.DecodeLM if isinstance(model, arpa_lm.ArpaLM) else \
+                ctc_fast.DecodeRNNLM if isinstance(model, nn_lm.RNNCharLM) else ctc_fast.DecodeNNLM
+            self._dev[key] = (cls(model, self.int_char_map, A), model)      # the model stays alive with its id
+        return self._dev[key][0]
+
+    def decode_batch(self, probs_list, beam=40, alpha=1.0, beta=0.0, nbest=1, rescore_lm=None, rescore_alpha=None,
+                     rescore_beta=None, rescore_nbest=None):
         """[(hyp, score)] for a list of (A, T) log-probability arrays, one launch; with nbest > 1 a list
-        of nbest (hyp, score) per utterance, best first (ranks beyond the beam: '', -inf)"""
+        of nbest (hyp, score) per utterance, best first (ranks beyond the beam: '', -inf).
+
+        ``rescore_lm`` (a ctc_fast.Decode*LM, a model, or the path of an ARPA / .npz file): a second pass
+        (``ctc_fast.rescore_nbest``) re-ranks the leading ``rescore_nbest`` hypotheses of every
+        utterance (default: all ``nbest``) by log P_ctc + rescore_alpha * log10 P_LM + rescore_beta * length under that
+        LM (the weights default to the first pass's) and returns them in the new order with the new scores; the
+        ranks it leaves alone follow with their first-pass scores.  ``self.rescore_changed`` then says, per
+        utterance, whether the 1-best changed."""
         if int(beam) < 0:
             raise OverflowError("can't convert negative value to unsigned int")
         for p in probs_list:
@@ -137,6 +163,21 @@ class BeamLMDecoder(DecoderBase):
         A = probs_list[0].shape[0]
         ids, scores = ctc_fast.decode_beam_batch(probs_list, beam=beam, alpha=alpha, beta=beta,
                                                  lm=self._device_lm(A), nbest=nbest)
+        if rescore_lm is not None:
+            rows = ids if nbest > 1 else [[h] for h in ids]
+            first = np.array(scores, dtype=np.float64).reshape(len(rows), nbest)
+            seen = first.copy()
+            if rescore_nbest is not None:
+                if not 1 <= int(rescore_nbest) <= nbest:
+                    raise ValueError("decode_batch: rescore_nbest outside 1..nbest")
+                seen[:, int(rescore_nbest):] = -np.inf
+            order, res = ctc_fast.rescore_nbest(probs_list, rows, lm=self._rescore_lm(rescore_lm, A),
+                                                alpha=alpha if rescore_alpha is None else rescore_alpha,
+                                                beta=beta if rescore_beta is None else rescore_beta, scores=seen)
+            self.rescore_changed = [int(o[0]) != 0 for o in order]
+            out = [[(self._string(row[k]), float(res[b, k]) if seen[b, k] > -np.inf else float(first[b, k])) for k in o]
+                   for b, (row, o) in enumerate(zip(rows, order))]
+            return out if nbest > 1 else [r[0] for r in out]
         if nbest > 1:
             return [[(self._string(h), float(s)) for h, s in zip(row, srow)] for row, srow in zip(ids, scores)]
         return [(self._string(h), float(s)) for h, s in zip(ids, scores)]

@@ -29,6 +29,11 @@ left open), and adds a line that counts the search errors (refscore > hypscore) 
 that cannot be aligned.  ``--ctm FILE [--frame-shift 0.01]`` writes the 1-best hypotheses as a CTM
 (swbd-utils/convert_to_ctm.py:21-37) with the time of every word taken from the forced alignment of
 the hypothesis (ctc_fast.align_batch): words are the runs of labels between ``--space`` symbols.
+
+``--rescore-lm FILE --rescore-nbest K [--rescore-alpha --rescore-beta]`` (character method, K <= beam) adds a
+second pass (ctc_fast.rescore_nbest): the K best hypotheses of the search are re-ranked under the
+LM of FILE (ARPA, or the .npz of a neural LM) with the full CTC sum; the hypothesis file and the CER are those of the
+re-ranked 1-best, and the summary says how many utterances changed their 1-best.
 """
 import argparse
 import os
@@ -252,6 +257,11 @@ def main(argv=None):
                     help="write a CTM with the time of every word of the 1-best hypotheses, from their forced "
                          "alignment (character method)")
     ap.add_argument("--frame-shift", type=float, default=0.01, help="seconds per frame (--ctm)")
+    ap.add_argument("--rescore-lm", metavar="FILE",
+                    help="second pass: re-rank the --rescore-nbest best hypotheses under this LM (character method)")
+    ap.add_argument("--rescore-nbest", type=int, default=0, metavar="K", help="hypotheses re-ranked per utterance, K <= beam")
+    ap.add_argument("--rescore-alpha", type=float, default=None, help="LM weight of the second pass (default --alpha)")
+    ap.add_argument("--rescore-beta", type=float, default=None, help="length bonus of the second pass (default --beta)")
     a = ap.parse_args(argv)
     K = a.nbest_oracle
     if K and a.method == "bg":
@@ -260,6 +270,11 @@ def main(argv=None):
         ap.error("--ref-scores and --ctm are for the character method")
     if K and not 1 <= K <= a.beam:
         ap.error("--nbest-oracle K needs 1 <= K <= beam")
+    Kr = a.rescore_nbest
+    if (a.rescore_lm or Kr) and a.method == "bg":
+        ap.error("--rescore-lm is for the character method")
+    if bool(a.rescore_lm) != bool(Kr) or (Kr and not 1 <= Kr <= a.beam):
+        ap.error("--rescore-lm FILE needs --rescore-nbest K with 1 <= K <= beam, and the other way round")
     with open(a.likelihoods, "rb") as f:
         ll = pickle.load(f)
     if a.method == "bg":
@@ -273,15 +288,20 @@ def main(argv=None):
     dec.load_chars(a.chars)
     dec.load_lm(a.lm)
     keys = sorted(ll)
-    errs = n_ref = oracle_errs = 0
+    errs = n_ref = oracle_errs = n_changed = 0
     space_id = dec.char_int_map.get(a.space)
     with open(a.out, "w") as out, ErrorLog(a.errors) as log, RefScoreLog(a.ref_scores) as ref_log, \
             open(a.ctm or os.devnull, "w") as ctm:
         for g in range(0, len(keys), a.batch):
             ks = keys[g:g + a.batch]
             probs = [np.asfortranarray(ll[k], dtype=np.float64) for k in ks]
-            res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, 1))
-            if K <= 1:
+            if Kr:
+                res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, Kr), rescore_lm=a.rescore_lm,
+                                       rescore_alpha=a.rescore_alpha, rescore_beta=a.rescore_beta, rescore_nbest=Kr)
+                n_changed += sum(dec.rescore_changed)
+            else:
+                res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, 1))
+            if max(K, Kr) <= 1:
                 res = [[r] for r in res]
             if ref_log.f:       # the transcripts of the batch under the search's objective, one call
                 idx = [i for i, k in enumerate(ks) if k in alis]
@@ -319,6 +339,8 @@ def main(argv=None):
     print("decoded %d utterances, CER %.4f (%d / %d)" % (len(keys), cer, errs, n_ref))
     log.summary()
     ref_log.summary()
+    if Kr:
+        print("rescored: %d of %d utterances changed their 1-best" % (n_changed, len(keys)))
     if K:
         print("oracle CER of %d-best %.4f (%d / %d), 1-best CER %.4f (%d / %d)"
               % (K, oracle_errs / float(max(n_ref, 1)), oracle_errs, n_ref, cer, errs, n_ref))
