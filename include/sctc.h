@@ -559,6 +559,59 @@ int sctc_nbest_rank_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_
                           const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
                           const double* first_scores_dev, double* rescored_dev, int32_t* order_dev, void* stream);
 
+/* ---- CTC loss on a time-major [T, N, C] tensor: what torch.nn.functional.ctc_loss takes (ctc_torch.py) -----
+ * Added without an ABI version bump (still 6): sctc_ctc_tnc_probs, sctc_ctc_tnc_empty, sctc_ctc_tnc_grad
+ * (DESIGN.md §4.13).
+ *
+ * A contiguous [T * N][C] buffer is a batch of sctc_ctc_loss_batch as it stands: frame t of utterance n is row
+ * rowbase_dev[t] + frame_off[n] with rowbase[t] = t * N, frame_off[n] = n, ld = C.  The three entries are what
+ * surrounds that call: the prologue that fills the buffer from a tensor of any strides, the utterances with an empty
+ * target (U == 0, which sctc_ctc_loss_batch rejects and torch.nn.functional.ctc_loss allows), and the backward pass
+ * of the autograd function.  T_n_dev (device int32 [N], 1..T) holds the frames of every utterance: rows of the padded
+ * frames t >= T_n[n] are never read, and written only by sctc_ctc_tnc_grad (zeros).  None of the kernels uses atomics
+ * or waits for another workgroup: each is deterministic bit for bit. */
+
+#define SCTC_TNC_LOG_PROBS 0  /* the input holds log-probabilities (torch.nn.functional.ctc_loss): p = exp(x) */
+#define SCTC_TNC_LOGITS 1     /* unnormalised activations: p = softmax of the row, the arithmetic of sctc_softmax_rows */
+
+typedef struct sctc_tnc_config {
+    int32_t T, N, C;              /* frames, utterances (>= 0), alphabet incl. the blank (>= 1); T * N <= INT32_MAX */
+    int32_t dtype;                /* SCTC_F32 | SCTC_F64: type of the strided tensor, of probs and of the gradient rows */
+    int32_t mode;                 /* SCTC_TNC_LOG_PROBS | SCTC_TNC_LOGITS */
+    int32_t blank;                /* blank id, 0..C-1 (torch.nn.CTCLoss(blank=)) */
+    int64_t stride_t, stride_n, stride_c;   /* element strides of the strided [T, N, C] tensor: the input of
+                                               sctc_ctc_tnc_probs, the output of sctc_ctc_tnc_grad */
+} sctc_tnc_config;
+
+/* All three: SCTC_ERR_ARG (no device needed) for a NULL config, T < 0, N < 0, C < 1, a blank outside [0, C), an
+ * unknown dtype or mode, T * N beyond INT32_MAX (rowbase is int32), and a NULL pointer with work to do.  T == 0 or
+ * N == 0 launches nothing.  No entry allocates device memory; every launch goes to `stream`. */
+
+/* The prologue of ctc_torch.ctc_loss: probs_dev [T * N][C] (contiguous) from the strided input_dev, row t * N + n
+ * for t < T_n[n].  A row per lane for C <= 32, a row per wave beyond. */
+int sctc_ctc_tnc_probs(const sctc_tnc_config* cfg, const void* input_dev, const int32_t* T_n_dev, void* probs_dev,
+                       void* stream);
+
+/* Utterances with an empty target, one wave each: idx_dev (device int32 [n_idx], 0 <= n_idx <= N) lists them.
+ * cost_dev[n] = -sum_t log p[t, n, blank], summed in float64 in ascending t; grad_dev rows p[t, n, :] - onehot(blank)
+ * (layout of probs_dev); skip_dev[n] = 1 and cost +inf if a p[t, n, blank] is 0, else 0.  cost_dev double [N],
+ * skip_dev int32 [N]: only the listed entries are written.  n_idx == 0 launches nothing.
+ * sym_dev (device int32 [n_idx], 0..C-1, or NULL: the blank for all): the symbol that listed utterance i emits in
+ * every frame, in place of the blank.  It serves the one other utterance with a single alignment, one label in one
+ * frame (T_n == 1, U == 1): PyTorch's loss there is -log p[0, n, label], while ctc_fast.pyx:42-47 normalises frame 0
+ * over the blank and the label before any band applies and returns -log(p_blank + p_label), and so does
+ * sctc_ctc_loss_batch. */
+int sctc_ctc_tnc_empty(const sctc_tnc_config* cfg, const void* probs_dev, const int32_t* T_n_dev, const int32_t* idx_dev,
+                       const int32_t* sym_dev, int32_t n_idx, void* grad_dev, double* cost_dev, int32_t* skip_dev,
+                       void* stream);
+
+/* The backward pass of ctc_torch.ctc_loss: out[t, n, c] (strided) = scale_dev[n] * grad_dev[t * N + n][c] (one
+ * float64 product, rounded once) where t < T_n[n], skip_dev[n] == 0 and cost_dev[n] is finite; exactly 0 elsewhere,
+ * by select: the gradient rows of the other frames and utterances are not read (they may hold anything, NaN
+ * included).  scale_dev double [N]. */
+int sctc_ctc_tnc_grad(const sctc_tnc_config* cfg, const void* grad_dev, const int32_t* T_n_dev, const double* cost_dev,
+                      const int32_t* skip_dev, const double* scale_dev, void* out_dev, void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

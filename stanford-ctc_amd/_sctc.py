@@ -116,6 +116,15 @@ LM_SCORE_TILE = 32          # csrc/lm_score_plan.h: sequences (recurrent LM) or 
 LM_SCORE_RESIDENT = 512     # resident tiles of a neural LM, each with its own scratch
 NBEST_MAX_K = 256
 
+class TncConfig(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_int32), ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("blank", ctypes.c_int32), ("stride_t", ctypes.c_int64),
+                ("stride_n", ctypes.c_int64), ("stride_c", ctypes.c_int64)]
+
+
+TNC_LOG_PROBS, TNC_LOGITS = 0, 1
+TNC_LANE_MAX_C = 32         # csrc/ctc_tnc.hip: rows up to this take a row per lane in the prologue, wider ones a row per wave
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -180,6 +189,9 @@ PROTOTYPES = {
     "sctc_lm_score_batch": (ctypes.c_int, [ctypes.POINTER(LmScoreConfig), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "sctc_nbest_rank_batch": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p, ctypes.c_double,
                                              ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "sctc_ctc_tnc_probs": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp]),
+    "sctc_ctc_tnc_empty": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]),
+    "sctc_ctc_tnc_grad": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, vp, vp, vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),
