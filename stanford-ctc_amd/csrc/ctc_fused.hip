@@ -45,6 +45,9 @@
 // IEEE division), formed once per symbol and frame, off the recursion's dependency chain.  The sums themselves
 // are taken as fixed trees (bit-reproducible run to run; the reference adds in ascending state
 // order: differences are in the last bits, the float64 golden vectors hold at 1e-11 / 1e-9).
+//
+// From ctc_dev.h: the reciprocals, the row gather / broadcast (RI and float64), the clamped row load, the
+// lane's sum tree and llForward's running product (LogProduct).
 #include <mutex>
 #include <type_traits>
 
@@ -54,9 +57,9 @@
 #endif
 
 #include "common.h"
+#include "ctc_dev.h"
 #include "ctc_kernels.h"
 #include "ctc_store.h"
-#include "xlane.h"
 
 namespace sctc {
 
@@ -151,7 +154,7 @@ void ctc_fused_kernel(CtcFusedArgs<RI> p)
     RI* grad = p.grad;
     const int64_t ld = p.ld;
 
-    // ---- per-lane constants: labels of my odd states, skip-transition permission (ctc_lattice_kernel)
+    // ---- per-lane constants: labels of my odd states, skip-transition permission (the same in all three kernels)
     int lab[KH];
     bool allow[KH], valid_lab[KH], valid_blk[KH];
     R allowf[KH];
@@ -222,93 +225,33 @@ void ctc_fused_kernel(CtcFusedArgs<RI> p)
         __builtin_amdgcn_wave_barrier();
         asm volatile("" ::: "memory");
     };
-    // NO load or store of the frame loops sits under a branch, not even a lane mask (round 6): behind control flow the
-    // compiler no longer knows how many memory operations are in flight and every later wait becomes s_waitcnt vmcnt(0)
-    // -- a block's prefetch then waited for the rows (phase 0) or gradient rows (phase 1) stored behind the block before,
-    // an HBM write round trip per block of frames (found in ctc_fusedw.hip, where it cost 1.3 us per block).  Columns and
-    // rows are clamped and masked by a select; lanes / frames with nothing to store write to the pad in front of the
-    // utterance's rows, which nobody reads unmasked.
-    auto load_row = [&](int64_t row, RI (&dst)[NA]) {
-        const RI* yr = probs + row * ld;
-#pragma unroll
-        for (int q = 0; q < NA; ++q) {
-            const int k = lane + 64 * q;
-            const RI v = yr[min(k, A - 1)];
-            dst[q] = k < A ? v : (RI)0;
-        }
-    };
+    // the kernel's context bound to the shared device code (ctc_dev.h); no load or store of the frame loops under a
+    // branch: lanes / frames with nothing to store write to the pad in front of the utterance's rows, which nobody reads
+    // unmasked
+    auto load_row = [&](int64_t row, RI (&dst)[NA]) { load_row_clamped(probs, ld, A, lane, row, dst); };
     const int32_t* const rb_tab = p.rowbase ? p.rowbase : reinterpret_cast<const int32_t*>(p.utts);
+    // row indices of a whole block of frames (block_rows, ctc_dev.h) with the load unconditional: through rb_tab
     auto block_rows = [&](int tau0) -> int {
         const int tau = min(tau0 + lane, T - 1);
         const int t = dir ? T - 1 - tau : tau;
         const int v = rb_tab[p.rowbase ? t : 0];
         return p.rowbase ? v : t;
     };
-    auto gather = [&](const RI (&y)[NA], int k) -> R {
-        RI out = lane_gather(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            RI o = lane_gather(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return (R)out;   // probs.astype(np.float64), brnnet.py:175
-    };
-    auto bcast = [&](const RI (&y)[NA], int k) -> R {
-        RI out = lane_bcast(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            RI o = lane_bcast(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return (R)out;
-    };
-    auto gather_d = [&](const R (&y)[NA], int k) -> R {
-        R out = lane_gather(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            R o = lane_gather(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return out;
-    };
-    auto bcast_d = [&](const R (&y)[NA], int k) -> R {
-        R out = lane_bcast(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            R o = lane_bcast(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return out;
-    };
+    auto gather = [&](const RI (&y)[NA], int k) -> R { return (R)row_gather(y, k); };   // probs.astype(np.float64), brnnet.py:175
+    auto bcast = [&](const RI (&y)[NA], int k) -> R { return (R)row_bcast(y, k); };
+    auto gather_d = [&](const R (&y)[NA], int k) -> R { return row_gather(y, k); };
+    auto bcast_d = [&](const R (&y)[NA], int k) -> R { return row_bcast(y, k); };
     // the other direction's row of MY frame tau: its own time index is T-1-tau, its state order mine mirrored
     auto load_other = [&](int tau, BlkU& dst) {
         const int taup = T - 1 - min(tau, T - 1);
         // (a lane beyond the row reads the K elements in front of it; products masks them)
         dst = *reinterpret_cast<const BlkU*>(other + (int64_t)taup * stride + other_off);
     };
-    auto recip = [&](R c) -> R {   // ctc_lattice_kernel: hardware estimate + two Newton-Raphson steps (<= 1 ulp)
-        R x = __builtin_amdgcn_rcp(c);
-        R e = fma(-c, x, (R)1);
-        x = fma(x, e, x);
-        e = fma(-c, x, (R)1);
-        return fma(x, e, x);
-    };
-    // 1/y for absum's per-state division (:125-131); y == 0 only ever meets a product that is exactly zero
-    // (the reference's `ab != 0` guard).  float32 probabilities are normal float64 numbers: the Newton
-    // reciprocal; float64 probabilities may be denormal: the IEEE division.
-    auto recip_or_zero = [&](R y) -> R {
-        if constexpr (sizeof(RI) == 4) {
-            const R r = recip(y);
-            return y > (R)0 ? r : (R)0;
-        } else {
-            return y > (R)0 ? (R)1 / y : (R)0;
-        }
-    };
-    auto local_sum = [&](const R (&n)[K]) -> R {
-        if constexpr (K == 8) return ((n[0] + n[1]) + (n[2] + n[3])) + ((n[4] + n[5]) + (n[6] + n[7]));
-        if constexpr (K == 2) return n[0] + n[1];
-        else return (n[0] + n[1]) + (n[2] + n[3]);
-    };
+    // (forwarding lambdas on purpose, like gather_d / bcast_d above: with the shared functions called directly at the
+    // call sites the compiler ordered the floating-point instructions of 16 of this file's 42 kernels differently)
+    auto recip = [&](R c) -> R { return ctc_recip(c); };
+    auto recip_or_zero = [&](R y) -> R { return ctc_recip_or_zero<RI>(y); };
+    auto local_sum = [&](const R (&n)[K]) -> R { return sum_tree(n); };
     auto quad_xor = [&](R v, auto ctrl_tag) -> R {
         constexpr int CTRL = decltype(ctrl_tag)::value;
         long long bits = __double_as_longlong(v);
@@ -323,25 +266,13 @@ void ctc_fused_kernel(CtcFusedArgs<RI> p)
     constexpr int NO_BAD = 0x7fffffff;
     int first_bad = NO_BAD;
     int skip = 0;
-    // llForward = sum_t log c_t (ctc_fast.pyx:47,76) = log of the product of the band sums c_t: the product is carried
-    // as mantissa x 2^exponent (three operations per frame, beside the recursion's chain) and its logarithm taken
-    // once; frames from the first zero band sum on do not count (the reference's exception leaves llForward as it
-    // was, :147-149).  The product of the c_t themselves, not of the applied factors 1/c_t: for T = 1 the cost is then
-    // the logarithm of the very double the reference takes it of (a cost of 1e-8 -- one frame, c = 1 - 1e-8 -- would
-    // otherwise carry the reciprocal's rounding: 2e-8 relative, found by the fuzz test).
-    R ll_m = (R)1;
-    int ll_e = 0;
-    auto ll_account = [&](R c) {
-        const R f = first_bad == NO_BAD ? c : (R)1;
-        ll_m *= f;
-        ll_e += __builtin_amdgcn_frexp_exp(ll_m);
-        ll_m = __builtin_amdgcn_frexp_mant(ll_m);
-    };
+    LogProduct llf;    // llForward; frames from the first zero band sum on do not count
+    auto ll_account = [&](R c) { llf.account(first_bad == NO_BAD ? c : (R)1); };
     // T < U: empty band at every frame t >= 1 -- the reference divides nothing, adds log(0) and
     // returns cost +inf, grad = params, skip False (ctc_fast.pyx:70-76 on an empty range)
     const bool empty_band = (L >= 2 * T + 2) && T > 1;
 
-    // one frame of the recursion; FAST: the band starts at state 0 (no band tests, ctc_lattice_kernel)
+    // one frame of the recursion; FAST: the band starts at state 0 (no band tests)
     auto step = [&](auto fast_tag, int tau, R yb, const R (&yl)[KH]) {
         constexpr bool FAST = decltype(fast_tag)::value;
         const R prev_last = lane_shr1(a[K - 1]);
@@ -369,7 +300,7 @@ void ctc_fused_kernel(CtcFusedArgs<RI> p)
                 n[2 * jj + 1] = (valid_lab[jj] && sb + 1 >= start) ? vl : (R)0;
             }
         }
-        const R c = wave_sum(local_sum(n));
+        const R c = wave_sum(local_sum(n));   // one wave per direction: no cross-wave sum
         R r;
         if constexpr (FAST) {
             first_bad = (c == (R)0 && first_bad == NO_BAD) ? tau : first_bad;   // ZeroDivisionError at :75
@@ -871,14 +802,8 @@ void ctc_fused_kernel(CtcFusedArgs<RI> p)
     }
 
     if (wave == 0 && lane == 0) {
-        // -llForward (ctc_fast.pyx:149,152); math.log(0.0) for the empty band.  Mantissa in [sqrt(1/2), sqrt(2)): a
-        // product near 1 has exponent 0 and its logarithm no cancellation against exponent x ln 2
-        if (ll_m < 0.70710678118654752440) {
-            ll_m *= 2.0;
-            ll_e -= 1;
-        }
-        double cost = -(log(ll_m) + (double)ll_e * 0.693147180559945309417232121458);
-        if (empty_band && !skip) cost = INFINITY;
+        double cost = llf.neg_log();
+        if (empty_band && !skip) cost = INFINITY;   // math.log(0.0)
         sh_cost = cost;
     }
     if (lane == 0 && !helper) sh_skip[dir] = skip;

@@ -32,13 +32,17 @@
 //
 // Summation order: as in ctc_fused.hip fixed trees / fixed list order (bit-reproducible run to run, last-bit
 // differences against the reference's ascending-state loop; the float64 golden vectors hold at 1e-11 / 1e-9).
+//
+// From ctc_dev.h: the reciprocals, the row gather / broadcast, the clamped row load and the block's row indices, the
+// cross-wave band sum with its boundary state (CrossWave), the LDS-only
+// barrier, the lane's sum tree and llForward's running product (LogProduct).
 #include <mutex>
 #include <type_traits>
 
 #include "common.h"
+#include "ctc_dev.h"
 #include "ctc_kernels.h"
 #include "ctc_store.h"
-#include "xlane.h"
 
 namespace sctc {
 
@@ -55,7 +59,7 @@ __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, 
     constexpr int NT = 64 * W;                               // global lanes of a direction
     constexpr int PF = NA * (int)sizeof(RI) >= 16 ? 4 : 8;   // phase 1: frames per block (prefetch depth, frames finished together)
     // phase 0 has no partner rows and no lists in flight: longer blocks there (gfx950 counts loads and stores in one
-    // in-order counter, so a block's prefetch also waits for the rows stored before it: once per block, ctc_lattice_kernel)
+    // in-order counter, so a block's prefetch also waits for the rows stored before it: once per block)
     constexpr int PF0 = NA * (int)sizeof(RI) >= 8 ? PF : 16;
     constexpr int NST = NT * K;                              // states a direction's lanes hold (> 2U+1: state NST-1 never exists)
     constexpr int NLB = NST / 2;                             // an LDS row of alpha*beta: [NLB blank states][NLB label states]
@@ -66,8 +70,7 @@ __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, 
     using BlkU = RowBlockU<ST, K>;
     using BlkA = RowBlockA<ST, K>;
 
-    // per frame parity and wave: {band-sum partial, last state's unnormalised value} (ctc_lattice_kernel)
-    __shared__ __attribute__((aligned(16))) double xw[2][W][2];
+    __shared__ __attribute__((aligned(16))) typename CrossWave<W>::Slots xw;
     __shared__ int32_t sh_word;
     extern __shared__ __attribute__((aligned(16))) double dyn_s[];
     double* const ab_s = dyn_s;                                               // [PF][NST] alpha*beta of a block's frames, by state
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, 
     RI* grad = p.grad;
     const int64_t ld = p.ld;
 
-    // ---- per-lane constants: labels of my odd states, skip-transition permission (ctc_lattice_kernel)
+    // ---- per-lane constants: labels of my odd states, skip-transition permission (the same in all three kernels)
     int lab[KH];
     bool allow[KH], valid_lab[KH], valid_blk[KH];
     R allowf[KH];
@@ -151,117 +154,40 @@ __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, 
         maxlen = wave_max(maxlen);
     };
 
-    // NO load or store of the frame loops sits under a branch, not even a lane mask: behind control flow the compiler
-    // no longer knows how many memory operations are in flight and turns every later wait into s_waitcnt vmcnt(0) -- the
-    // loop's register rotation then waited for the gradient row stored a moment before, an HBM write round trip per
-    // block of frames (1.3 us per block of 8: the first version of phase 1).  Columns are clamped and masked by a
-    // select, rows beyond the end are clamped, lanes that have nothing to store write to a dump area.
-    auto load_row = [&](int64_t row, RI (&dst)[NA]) {
-        const RI* yr = probs + row * ld;
-#pragma unroll
-        for (int q = 0; q < NA; ++q) {
-            const int k = lane + 64 * q;
-            const RI v = yr[min(k, A - 1)];
-            dst[q] = k < A ? v : (RI)0;
-        }
-    };
-    // row indices of a whole block of frames with one vector load (lane i <- frame tau0 + i, clamped)
-    auto block_rows = [&](int tau0) -> int {
-        const int tau = min(tau0 + lane, T - 1);
-        const int t = dir ? T - 1 - tau : tau;
-        return (p.rowbase ? p.rowbase[t] : t);
-    };
-    auto gather = [&](const RI (&y)[NA], int k) -> R {
-        RI out = lane_gather(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            RI o = lane_gather(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return (R)out;   // probs.astype(np.float64), brnnet.py:175
-    };
-    auto bcast = [&](const RI (&y)[NA], int k) -> R {
-        RI out = lane_bcast(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            RI o = lane_bcast(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return (R)out;
-    };
+    // the kernel's context bound to the shared device code (ctc_dev.h); no load or store of the frame loops under a branch
+    auto load_row = [&](int64_t row, RI (&dst)[NA]) { load_row_clamped(probs, ld, A, lane, row, dst); };
+    auto block_rows = [&](int tau0) -> int { return sctc::block_rows(p.rowbase, T, dir, lane, tau0); };
+    auto gather = [&](const RI (&y)[NA], int k) -> R { return (R)row_gather(y, k); };   // probs.astype(np.float64), brnnet.py:175
+    auto bcast = [&](const RI (&y)[NA], int k) -> R { return (R)row_bcast(y, k); };
     // the other direction's row of MY frame tau: its own time index is T-1-tau, its state order mine mirrored
     auto load_other = [&](int tau, BlkU& dst) {
         const int taup = T - 1 - min(tau, T - 1);
         // (a lane beyond the row reads the K elements in front of it -- finite values that meet zeros, see products)
         dst = *reinterpret_cast<const BlkU*>(other + (int64_t)taup * stride + other_off);
     };
-    auto recip = [&](R c) -> R {   // ctc_lattice_kernel: hardware estimate + two Newton-Raphson steps (<= 1 ulp)
-        R x = __builtin_amdgcn_rcp(c);
-        R e = fma(-c, x, (R)1);
-        x = fma(x, e, x);
-        e = fma(-c, x, (R)1);
-        return fma(x, e, x);
-    };
-    auto recip_or_zero = [&](R y) -> R {     // ctc_fused.hip: 1/y for absum's per-state division (:125-131)
-        if constexpr (sizeof(RI) == 4) {
-            const R r = recip(y);
-            return y > (R)0 ? r : (R)0;
-        } else {
-            return y > (R)0 ? (R)1 / y : (R)0;
-        }
-    };
-    auto local_sum = [&](const R (&n)[K]) -> R {
-        if constexpr (K == 2) return n[0] + n[1];
-        else return (n[0] + n[1]) + (n[2] + n[3]);
-    };
-    // workgroup barrier that orders LDS traffic only (ctc_lattice_kernel): __syncthreads() would also drain the
-    // row / gradient stores to HBM in every frame
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    // (forwarding lambdas on purpose: with the shared functions called directly at the call sites the compiler ordered
+    // the floating-point instructions of 19 of this file's 36 kernels differently)
+    auto recip = [&](R c) -> R { return ctc_recip(c); };
+    auto recip_or_zero = [&](R y) -> R { return ctc_recip_or_zero<RI>(y); };
+    auto local_sum = [&](const R (&n)[K]) -> R { return sum_tree(n); };
 
     R a[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) a[j] = (R)0;
-    R bprev = (R)0;    // the previous wave's last state, unnormalised, as of the last frame
+    CrossWave<W> cw;   // band sums over the W waves and the previous wave's boundary state: ONE barrier per frame
     R rprev = (R)1;    // factor the previous frame's row was scaled with
     constexpr int NO_BAD = 0x7fffffff;
     int first_bad = NO_BAD;
     int skip = 0;
-    // llForward as the logarithm of the running product of the band sums (ctc_fused.hip)
-    R ll_m = (R)1;
-    int ll_e = 0;
-    auto ll_account = [&](R c) {
-        const R f = first_bad == NO_BAD ? c : (R)1;
-        ll_m *= f;
-        ll_e += __builtin_amdgcn_frexp_exp(ll_m);
-        ll_m = __builtin_amdgcn_frexp_mant(ll_m);
-    };
+    LogProduct llf;    // llForward; frames from the first zero band sum on do not count
+    auto ll_account = [&](R c) { llf.account(first_bad == NO_BAD ? c : (R)1); };
     const bool empty_band = (L >= 2 * T + 2) && T > 1;
-
-    // band sum of a frame over all W waves, identical in every lane (fixed order); leaves the boundary state the NEXT
-    // frame needs in bprev (ONE barrier per frame, ctc_lattice_kernel)
-    auto block_sum = [&](R loc, R last_unnorm, int tau) -> R {
-        const R ws = wave_sum(loc);
-        if (lane == 63) *reinterpret_cast<double2*>(&xw[tau & 1][wave][0]) = make_double2(ws, last_unnorm);
-        lds_barrier();
-        R pw[W];
-#pragma unroll
-        for (int w = 0; w < W; ++w) pw[w] = xw[tau & 1][w][0];
-        bprev = xw[tau & 1][wave > 0 ? wave - 1 : 0][1];
-#pragma unroll
-        for (int st = 1; st < W; st *= 2)
-#pragma unroll
-            for (int w = 0; w + st < W; w += 2 * st) pw[w] += pw[w + st];
-        return pw[0];
-    };
+    auto block_sum = [&](R loc, R last_unnorm, int tau) -> R { return cw.sum(xw, loc, last_unnorm, tau, lane, wave); };
 
     // one frame of the recursion; FAST: the band starts at state 0 (no band tests)
     auto step = [&](auto fast_tag, int tau, R yb, const R (&yl)[KH]) {
         constexpr bool FAST = decltype(fast_tag)::value;
-        R prev_last = lane_shr1(a[K - 1]);
-        {
-            const R across = bprev * rprev;          // the very product the owning wave formed
-            prev_last = (lane == 0 && wave > 0) ? across : prev_last;
-        }
+        const R prev_last = cw.shift_in(a[K - 1], rprev, lane, wave);
         R n[K];
         if constexpr (FAST) {
 #pragma unroll
@@ -592,13 +518,8 @@ __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, 
     timed_out |= got == 0;
     const int any_skip = mine_skip | (got == 2 ? 1 : 0);
     if (dir == 0 && threadIdx.x == 0) {
-        // -llForward (ctc_fast.pyx:149,152); math.log(0.0) for the empty band (ctc_fused.hip)
-        if (ll_m < 0.70710678118654752440) {
-            ll_m *= 2.0;
-            ll_e -= 1;
-        }
-        double cost = -(log(ll_m) + (double)ll_e * 0.693147180559945309417232121458);
-        if (empty_band && !mine_skip) cost = INFINITY;
+        double cost = llf.neg_log();   // -llForward (ctc_fast.pyx:149,152)
+        if (empty_band && !mine_skip) cost = INFINITY;   // math.log(0.0)
         if (timed_out) cost = NAN;
         p.cost[b] = cost;
         p.skip[b] = any_skip;

@@ -17,9 +17,11 @@
 //                         other label's sum along its host-built list of states (ascending, the
 //                         reference's order, ctc_fast.pyx:120-131).
 //   softmax_rows_generic  three passes over a row of any width.
+//
+// From ctc_dev.h: frame_row and the row scaling's reciprocal (ctc_recip).
 #include "common.h"
+#include "ctc_dev.h"
 #include "ctc_kernels.h"
-#include "xlane.h"
 
 namespace sctc {
 
@@ -31,20 +33,6 @@ constexpr int GEN_NW = GEN_NT / 64;
 __device__ __forceinline__ double ld_l2(const double* p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int64_t gen_frame_row(const CtcUtt& u, const int32_t* rowbase, int t)
-{
-    return rowbase ? (int64_t)rowbase[t] + u.row0 : u.row0 + t;
-}
-
-__device__ __forceinline__ double gen_recip(double c)   // ctc_lattice_kernel's reciprocal
-{
-    double x = __builtin_amdgcn_rcp(c);
-    double e = fma(-c, x, 1.0);
-    x = fma(x, e, x);
-    e = fma(-c, x, 1.0);
-    return fma(x, e, x);
 }
 
 // sum over the workgroup, identical in every thread, fixed order; `slot` alternates by caller
@@ -82,9 +70,9 @@ __global__ __launch_bounds__(GEN_NT) void ctc_lattice_generic_kernel(CtcLatticeA
     };
     auto probs_row = [&](int tau) -> const RI* {
         const int t = dir ? T - 1 - tau : tau;
-        return p.probs + gen_frame_row(u, p.rowbase, t) * p.ld;
+        return p.probs + frame_row(u, p.rowbase, t) * p.ld;
     };
-    const bool empty_band = (L >= 2 * T + 2) && T > 1;   // ctc_lattice_kernel: cost +inf, skip False
+    const bool empty_band = (L >= 2 * T + 2) && T > 1;   // T < U: cost +inf, skip False (ctc_fast.pyx:70-76 on an empty range)
 
     int skip = 0, n_rows = T;
     double rprev = 1.0;
@@ -97,14 +85,14 @@ __global__ __launch_bounds__(GEN_NT) void ctc_lattice_generic_kernel(CtcLatticeA
             skip = 1;   // ZeroDivisionError at :45
             n_rows = 0;
         } else {
-            rprev = gen_recip(c);
+            rprev = ctc_recip(c);
         }
         for (int s = tid; s < L; s += GEN_NT) {
             const double v = s == 0 ? a0 : (s == 1 ? a1 : 0.0);
             sc[s] = v;
             lat[s] = v * rprev;
         }
-        if (tid == 0) lat[LP - 1] = skip ? 1.0 : c;   // the band sum itself: llForward takes its logarithm (ctc_kernels.hip)
+        if (tid == 0) lat[LP - 1] = skip ? 1.0 : c;   // the band sum itself: llForward takes its logarithm (LogProduct, ctc_dev.h, has the why)
     }
     __syncthreads();
     for (int tau = 1; tau < T && !skip; ++tau) {
@@ -141,14 +129,14 @@ __global__ __launch_bounds__(GEN_NT) void ctc_lattice_generic_kernel(CtcLatticeA
                 n_rows = tau;
                 break;
             }
-            r = gen_recip(c);
+            r = ctc_recip(c);
         }
         double* row = lat + (int64_t)tau * LP;
         for (int s = tid; s < L; s += GEN_NT) row[s] = ld_l2(cur + s) * r;
         if (tid == 0) row[LP - 1] = empty_band ? 1.0 : c;
         rprev = r;
     }
-    // llForward = sum_t log c_t over the stored band sums (ctc_lattice_kernel's order)
+    // llForward = sum_t log c_t over the stored band sums: lane l takes frames l, l + 64, ... in ascending order
     __syncthreads();
     if (tid < 64) {
         double ll = 0.0;
@@ -175,7 +163,7 @@ __global__ __launch_bounds__(256) void ctc_grad_generic_kernel(CtcGradArgs<RI> p
         p.cost[b] = -p.ll[2 * b];   // -llForward, ctc_fast.pyx:149,152
         p.skip[b] = skip;
     }
-    const int64_t row = gen_frame_row(u, p.rowbase, t);
+    const int64_t row = frame_row(u, p.rowbase, t);
     const RI* y = p.probs + row * p.ld;
     RI* gr = p.grad + row * p.ld;
     if (skip) {   // the reference's zero-initialised grad (ctc_fast.pyx:31-32,149)

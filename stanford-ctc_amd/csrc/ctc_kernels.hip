@@ -22,20 +22,21 @@
 // s' order and read back reversed by ctc_grad.
 //
 // Scaling: the reference renormalises every frame by c_t = sum over the band
-// (ctc_fast.pyx:70-76).  We multiply by r ~ 1/c at the rescale points (see the lattice
-// kernel) and account llForward -= log(r) in float64, exact for whatever r was applied:
-// r is v_rcp_f64 + two Newton steps (half the dependent operations of the IEEE division
-// sequence, which sat on every frame's critical path), and the applied factors are not
-// tracked in registers but stored into the one lattice column no state ever occupies
-// (2U+1 is odd, the row stride even) and summed up after the last frame.
+// (ctc_fast.pyx:70-76).  We multiply by r ~ 1/c at the rescale points (r is v_rcp_f64 + two
+// Newton steps, ctc_recip) and take llForward = sum_t log c_t from the band sums themselves,
+// like the reference: they are not tracked in registers but stored into the one lattice
+// column no state ever occupies (2U+1 is odd, the row stride even), and their logarithms
+// are summed up after the last frame.
+//
+// From ctc_dev.h: the reciprocal, the row gather / broadcast, the predicated row load, frame_row, the cross-wave band
+// sum with its boundary state (CrossWave) and its LDS-only barrier.  The frame of the recursion is restated here.
 #include <type_traits>
 
 #include "common.h"
+#include "ctc_dev.h"
 #include "ctc_kernels.h"
-#include "xlane.h"
 
 namespace sctc {
-
 
 template <typename R>
 struct Vec;
@@ -144,11 +145,6 @@ int launch_argmax_rows(const void* y, int dtype, int32_t* best, int64_t rows, in
 
 // ---------------------------------------------------------------- ctc_lattice
 
-__device__ __forceinline__ int64_t frame_row(const CtcUtt& u, const int32_t* rowbase, int t)
-{
-    return rowbase ? (int64_t)rowbase[t] + u.row0 : u.row0 + t;
-}
-
 // K states per lane (even), NA = ceil(A/64) probability registers per frame.
 // RI: storage type of probs; the recursion itself runs in float64 (see ctc_kernels.h).
 //
@@ -165,13 +161,9 @@ __device__ __forceinline__ int64_t frame_row(const CtcUtt& u, const int32_t* row
 template <typename RI, int K, int NA, int W, bool LAZY>
 __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> p)
 {
-    // W waves share one (utterance, pass): state s lives in global lane gl = s / K.  The two
-    // cross-wave couplings of a frame go through LDS: the neighbour state of a wave's lane 0
-    // (last state of the previous wave) and the band sum of a rescaling frame.
-    // per frame parity and wave: {band-sum partial, last state's unnormalised value} -- one 16-byte slot,
-    // written by lane 63 with one ds_write_b128
-    __shared__ __attribute__((aligned(16))) double xw[2][W > 1 ? W : 1][2];
-    double bprev = 0.0;   // W > 1: the previous wave's last state as of the last exchange (read right behind its barrier)
+    // W waves share one (utterance, pass): the two cross-wave couplings of a frame go through LDS (CrossWave, ctc_dev.h)
+    __shared__ __attribute__((aligned(16))) typename CrossWave<W>::Slots xw;
+    CrossWave<W> cw;
     using R = double;
     static_assert(K % 2 == 0 && K >= 2, "K must be even");
     constexpr int KH = K / 2;
@@ -226,46 +218,22 @@ __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> 
     const int64_t ld = p.ld;
     const int A = p.A;
 
-    // a frame's probabilities stay in their storage type until they are gathered
-    auto load_row = [&](int64_t row, RI (&dst)[NA]) {
-        const RI* yr = probs + row * ld;
-#pragma unroll
-        for (int q = 0; q < NA; ++q) {
-            const int k = lane + 64 * q;
-            dst[q] = k < A ? yr[k] : (RI)0;
-        }
-    };
+    // the kernel's context bound to the shared device code (ctc_dev.h); a frame's probabilities stay in their storage
+    // type until they are gathered
+    auto load_row = [&](int64_t row, RI (&dst)[NA]) { load_row_predicated(probs, ld, A, lane, row, dst); };
     auto load_frame = [&](int tau, RI (&dst)[NA]) {
         const int t = dir ? T - 1 - tau : tau;
         load_row(frame_row(u, p.rowbase, t), dst);
     };
-    // Row indices of a whole block of frames with ONE vector load (lane i <- frame tau0 + i, clamped),
-    // fetched a block before they are needed.  Looking rowbase[t] up frame by frame put a dependent
-    // load and an s_waitcnt vmcnt(0) -- which also waits for every lattice-row store in flight -- in
-    // front of each prefetched frame: 1000 of the 1600 shader cycles a frame cost (s_memtime stamps).
+    // row indices of a whole block of frames with ONE vector load (block_rows, ctc_dev.h; restated: through the shared
+    // function two instantiations allocate registers differently)
     auto block_rows = [&](int tau0) -> int {
         const int tau = min(tau0 + lane, T - 1);
         const int t = dir ? T - 1 - tau : tau;
         return p.rowbase ? p.rowbase[t] : t;
     };
-    auto gather = [&](const RI (&y)[NA], int k) -> R {
-        RI out = lane_gather(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            RI o = lane_gather(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return (R)out;   // probs.astype(np.float64), brnnet.py:175
-    };
-    auto bcast = [&](const RI (&y)[NA], int k) -> R {
-        RI out = lane_bcast(y[0], k & 63);
-#pragma unroll
-        for (int q = 1; q < NA; ++q) {
-            RI o = lane_bcast(y[q], k & 63);
-            if ((k >> 6) == q) out = o;
-        }
-        return (R)out;
-    };
+    auto gather = [&](const RI (&y)[NA], int k) -> R { return (R)row_gather(y, k); };   // probs.astype(np.float64), brnnet.py:175
+    auto bcast = [&](const RI (&y)[NA], int k) -> R { return (R)row_bcast(y, k); };
     // A row is stored together with the factor it was scaled with: L = 2U+1 is odd and the row
     // stride LP even, so column LP-1 (last register of the last lane, always a zero state) is free.
     // Keeping the factors in registers instead -- one per lane, folded 64 at a time -- cost a lane
@@ -287,73 +255,14 @@ __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> 
             for (int j = 0; j < K; ++j) row[j] = j == K - 1 ? vlast : v[j];
         }
     };
-    // 1/c for the row scaling: hardware estimate + two Newton-Raphson steps (the reciprocal part of
-    // the IEEE division sequence without its scaling / fix-up tail; <= 1 ulp).  Which double is
-    // applied does not matter for parity: llForward takes the log of exactly this value, and the
-    // per-frame factors cancel in the gradient (ctc_fast.pyx:138-145).
-    auto recip = [&](R c) -> R {
-        R x = __builtin_amdgcn_rcp(c);
-        R e = fma(-c, x, (R)1);
-        x = fma(x, e, x);
-        e = fma(-c, x, (R)1);
-        return fma(x, e, x);
-    };
-
-    // workgroup barrier that orders LDS traffic only: __syncthreads() would also drain the
-    // lattice-row stores to HBM (vmcnt) in every frame
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-    // W > 1: ONE workgroup barrier per frame.  Before it every wave publishes its band-sum partial and
-    // its last state's UNNORMALISED value n[K-1]; after it every wave knows the frame's c (and r = 1/c),
-    // and the next frame's neighbour state of lane 0 is bnd * r -- the very multiplication the owning
-    // wave performs, so the lattice is bit-identical to the two-barrier schedule this replaces (publish
-    // the normalised boundary after the sum, meet again at the start of the next frame: 1.08 us per
-    // frame at T = 8000 / U = 800).  Slots alternate by frame parity: a wave that races ahead writes the
-    // other slot, and cannot reach this one again before everybody has passed the next barrier.
-    // sum over all states of the block, identical in every lane (fixed order)
-    auto block_sum = [&](R loc, R last_unnorm, int tau) -> R {
-        const R ws = wave_sum(loc);
-        if constexpr (W == 1) {
-            return ws;
-        } else {
-            if (lane == 63) {
-                *reinterpret_cast<double2*>(&xw[tau & 1][wave][0]) = make_double2(ws, last_unnorm);
-            }
-            lds_barrier();
-            // every read behind the barrier is issued at once: the W partials and the boundary state the
-            // NEXT frame needs (it used to be a dependent LDS read at the head of that frame); the partials
-            // are summed as a tree in a fixed order
-            R pw[W];
-#pragma unroll
-            for (int w = 0; w < W; ++w) pw[w] = xw[tau & 1][w][0];
-            bprev = xw[tau & 1][wave > 0 ? wave - 1 : 0][1];
-#pragma unroll
-            for (int st = 1; st < W; st *= 2)
-#pragma unroll
-                for (int w = 0; w + st < W; w += 2 * st) pw[w] += pw[w + st];
-            return pw[0];
-        }
-    };
-    // frames without a rescale (lazy schedule): the boundary state alone
-    auto publish = [&](R last, int tau) {
-        if constexpr (W > 1) {
-            if (lane == 63) xw[tau & 1][wave][1] = last;
-            lds_barrier();
-            bprev = xw[tau & 1][wave > 0 ? wave - 1 : 0][1];
-        }
-    };
-    // last state of global lane gl - 1 as of the previous frame (all threads call, start of a frame);
-    // rprev = the factor the previous frame's row was scaled with (1 if it was not)
-    auto shift_in = [&](const R (&v)[K], int tau, R rprev) -> R {
-        R prev = lane_shr1(v[K - 1]);
-        if constexpr (W > 1) {
-            (void)tau;
-            const R across = bprev * rprev;          // the very product the owning wave stored
-            prev = (lane == 0 && wave > 0) ? across : prev;
-        }
-        return prev;
-    };
-
-    // sum of a lane's K new states as a balanced tree (log2 K dependent additions instead of K-1)
+    // (a forwarding lambda on purpose, here and in the two fused kernels: with the shared functions called directly at
+    // the call sites the compiler ordered the floating-point instructions of 16 / 19 fused kernels differently)
+    auto recip = [&](R c) -> R { return ctc_recip(c); };
+    auto block_sum = [&](R loc, R last_unnorm, int tau) -> R { return cw.sum(xw, loc, last_unnorm, tau, lane, wave); };
+    auto publish = [&](R last, int tau) { cw.publish(xw, last, tau, lane, wave); };
+    auto shift_in = [&](const R (&v)[K], R rprev) -> R { return cw.shift_in(v[K - 1], rprev, lane, wave); };
+    // sum_tree of ctc_dev.h, restated (as is the frame of the recursion, see there): through shared functions 10 and
+    // 62 of this file's 101 kernels allocate registers differently (profiles/ctc_dev_refactor.md)
     auto local_sum = [&](const R (&n)[K]) -> R {
         R t[K];
 #pragma unroll
@@ -444,12 +353,7 @@ __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> 
                     }
                 }
             }
-            // Frames whose band starts at state 0 (L <= 2(T - tau): all but the last ~U frames)
-            // need no band test, and the states beyond the label row stay exactly zero because
-            // their label probability was zeroed at gather time (a blank state beyond the row
-            // only ever adds zeros).  For a whole block of such frames the step is 2 DPP moves,
-            // 5 float64 operations per state pair and the row store -- no compares or selects on
-            // the recursion's dependency chain.  `in + allow*below` as one fma rounds like the add.
+            // a whole block of frames whose band starts at state 0: no band tests (the FAST frames, ctc_dev.h)
             const bool fast = PREG && (tb + PF - 1 < T) && (L <= 2 * (T - (tb + PF - 1)));
             if (fast) {
                 if constexpr (PREG) {
@@ -457,7 +361,7 @@ __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> 
                     for (int i = 0; i < PF; ++i) {
                         const int tau = tb + i;
                         const R yb = ybv[i];
-                        const R prev_last = shift_in(a, tau, rprev);
+                        const R prev_last = shift_in(a, rprev);
                         R n[K];
 #pragma unroll
                         for (int jj = 0; jj < KH; ++jj) {
@@ -494,7 +398,7 @@ __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> 
                     const int start = L <= rem ? 0 : L - rem;
                     R yb;
                     if constexpr (PREG) yb = ybv[i]; else yb = bcast(ycur[i], blank);
-                    const R prev_last = shift_in(a, tau, rprev);  // state K*gl - 1
+                    const R prev_last = shift_in(a, rprev);  // state K*gl - 1
                     R n[K];
 #pragma unroll
                     for (int jj = 0; jj < KH; ++jj) {

@@ -159,8 +159,10 @@ def test_every_named_path_reaches_the_kernel_it_names(dump, name):
         elif name.startswith("wide"):
             W = 8 if name == "wide8" else 4
             assert got == ["ctc_fusedw_kernel<%s, %s, %d, %d, %d>" % (ri, rows, 2 if L <= 128 * W else 4, NA, W)], tag
-        elif name == "lattice":
+        elif name.startswith("lattice"):
             assert _is_lattice_pair(got, ri), tag
+            if name != "lattice":        # the forced shapes: that many waves per direction
+                assert _args(got[0])[3] == name[len("lattice"):], tag
         else:
             assert name == "generic"
             assert got == ["ctc_lattice_generic_kernel<%s>" % ri, "ctc_grad_generic_kernel<%s>" % ri], tag
@@ -182,6 +184,48 @@ def test_the_network_minibatches_take_the_wide_kernel_and_the_lattice_pair(dump)
         assert got == ["ctc_lattice_kernel<float, 4, 1, 8, false>", "ctc_grad_kernel<float, 16>"]
     # one utterance fewer than the 18: the lattice pair by default
     assert _is_lattice_pair(kernels(dump, {}, [(17, 33, 0, 1601, 8000)])[0], "float")
+
+
+def test_the_bit_pinned_cases_reach_every_instantiation(dump):
+    """tests/data/ctc_bits_parent.txt (test_outputs_are_bit_identical_to_the_recorded_parent): its cases run every value
+    of every template parameter of the four kernel families but the lattice kernel's lazy schedule (SCTC_CTC_LAZY is
+    not a path of path.ENV) -- of the lattice, gradient and generic kernels every instantiation -- with both blank
+    positions, a skipping input, an empty band and T = 1 on every path"""
+    cases = {c[0]: c for c in paths.bits_cases()}
+    recorded = [cases[l.split()[0]] for l in paths.bits_recorded()]
+    seen, per_path = set(), {}
+    for which in sorted(set(c[1] for c in recorded)):
+        mine = [c for c in recorded if c[1] == which]
+        queries = [(1, A, int(dt == np.float64), 2 * U + 1, T) for _, _, A, T, U, _, dt, _ in mine]
+        for c, got in zip(mine, kernels(dump, paths.path.ENV[which], queries)):
+            seen.update(got)
+        per_path[which] = mine
+    for which, mine in per_path.items():
+        assert {c[5] == 0 for c in mine} == {True, False}, which                          # both blank positions
+        assert {"skip", "empty"} <= {c[7] for c in mine} and any(c[3] == 1 for c in mine), which
+    want = set()
+    for ri, st in (("float", "unsigned int"), ("float", "double"), ("double", "double")):
+        for NA in (1, 2, 4):
+            for K in (2, 4, 8):
+                want.add("ctc_fused_kernel<%s, %s, %d, %d, false, false>" % (ri, st, K, NA))
+                if (NA == 1 and st == "unsigned int") if K == 8 else NA <= 2:
+                    want.add("ctc_fused_kernel<%s, %s, %d, %d, true, false>" % (ri, st, K, NA))
+            for K, W in ((2, 4), (4, 4), (2, 8), (4, 8)):
+                want.add("ctc_fusedw_kernel<%s, %s, %d, %d, %d>" % (ri, st, K, NA, W))
+    want |= {"ctc_fused_kernel<float, unsigned int, %d, 1, false, true>" % K for K in (2, 4)}
+    for ri in ("float", "double"):
+        for NA in (1, 2, 4):
+            for K, W in ((2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (2, 4), (4, 4), (8, 4), (2, 8), (4, 8)):
+                want.add("ctc_lattice_kernel<%s, %d, %d, %d, false>" % (ri, K, NA, W))
+        want |= {"ctc_grad_kernel<%s, %d>" % (ri, NB) for NB in (4, 8, 16)}
+        want |= {"ctc_lattice_generic_kernel<%s>" % ri, "ctc_grad_generic_kernel<%s>" % ri}
+    assert seen <= want, sorted(seen - want)
+    for family in sorted(set(n[:n.index("<")] for n in want)):
+        for i in range(len(_args(next(n for n in want if n.startswith(family + "<"))))):
+            values = lambda names: set(_args(n)[i] for n in names if n.startswith(family + "<"))
+            assert values(seen) == values(want), (family, i, values(want) - values(seen))
+    # the lattice, gradient and generic kernels: every instantiation
+    assert not [n for n in want - seen if not n.startswith("ctc_fused")], sorted(want - seen)
 
 
 # (text of csrc/ctc_plan.h, its replacement): each moves one threshold by one or two

@@ -12,7 +12,9 @@ against each other.  Tolerances: float64 probabilities 1e-11 relative on the cos
 (different summation order of the same float64 numbers); float32 probabilities with the fused kernel's 32-bit row
 store 2e-7 absolute on the gradient (22 mantissa bits on one factor of alpha*beta; the gradient itself is float32).
 """
+import hashlib
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -41,7 +43,11 @@ class path:
            "wide": {"SCTC_CTC_WIDE": "1"}, "wide8": {"SCTC_CTC_WIDE": "1", "SCTC_CTC_WAVES": "8"},
            "wide64": {"SCTC_CTC_WIDE": "1", "SCTC_CTC_STORE": "64"},
            "widemin1": {"SCTC_CTC_WIDE_MIN_B": "1"},      # the default dispatch (rows of 513..2048 states only) from one utterance on
-           "lattice": {"SCTC_CTC_FUSED": "0"}, "generic": {"SCTC_CTC_GENERIC": "1"}}
+           "lattice": {"SCTC_CTC_FUSED": "0"}, "generic": {"SCTC_CTC_GENERIC": "1"},
+           # the lattice kernel's forced shapes (ctc_lattice_shape: 8 / 16 / 32 states per lane on one wave, 8 on four
+           # waves, 2 on eight)
+           "lattice1": {"SCTC_CTC_FUSED": "0", "SCTC_CTC_WAVES": "1"}, "lattice4": {"SCTC_CTC_FUSED": "0", "SCTC_CTC_WAVES": "4"},
+           "lattice8": {"SCTC_CTC_FUSED": "0", "SCTC_CTC_WAVES": "8"}}
     VARS = ("SCTC_CTC_STORE", "SCTC_CTC_FUSED", "SCTC_CTC_GENERIC", "SCTC_CTC_HELPER", "SCTC_CTC_DIET_MIN_B", "SCTC_CTC_WIDE",
             "SCTC_CTC_WAVES", "SCTC_CTC_WIDE_MIN_B")
 
@@ -532,3 +538,86 @@ def test_tiny_cost_is_the_log_of_the_band_sum_itself(mods, which):
             if not s_ref and np.isfinite(c_ref):
                 assert abs(cost - c_ref) <= 1e-10 * abs(c_ref) + 1e-300, (which, T, U, cost, c_ref)
                 assert np.abs(grad - g_ref).max() < 1e-9
+
+
+# ---------------------------------------------------------------- bit-identical outputs, every kernel instantiation
+
+BITS_RECORDED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "ctc_bits_parent.txt")
+# label rows (U, T) by states per lane and waves: 61, 201, 401, 801 and 1201 lattice states
+_ROWS = {2: (30, 77), 4: (100, 230), 8: (200, 300), 16: (400, 520), 32: (600, 690)}
+_BITS_PATHS = [  # (path.ENV name, rows, alphabets, dtypes)
+    ("fused", (2, 4, 8), (33, 100, 200), "fd"), ("fused64", (2, 4, 8), (33, 100, 200), "f"),
+    ("fused2w", (2, 4, 8), (33, 100, 200), "fd"), ("fused2wd", (2, 4), (33,), "f"),
+    ("wide", (8, 16, 32), (33, 100, 200), "fd"), ("wide8", (8,), (33, 100, 200), "fd"), ("wide64", (8, 32), (33, 100, 200), "f"),
+    ("lattice", (2, 4, 8, 16, 32), (33, 100, 200), "fd"), ("lattice1", (8, 16, 32), (33, 100, 200), "fd"),
+    ("lattice4", (32,), (33, 100, 200), "fd"), ("lattice8", (8,), (33, 100, 200), "fd"), ("generic", (2,), (33,), "fd"),
+]
+
+
+def bits_cases():
+    """(name, path, A, T, U, blank, dtype, kind): per path every row width, alphabet width and dtype that selects another
+    kernel instantiation (tests/test_ctc_plan_cpu.py checks which), the blank id alternating between 0 and A - 1; then
+    per path an input that skips (a zero column in phase 1), an empty band (T < U) and T = 1"""
+    out = []
+    for which, rows, alphabets, dts in _BITS_PATHS:
+        shapes = [(A, _ROWS[r][1], _ROWS[r][0], "plain") for r in rows for A in alphabets]
+        shapes += [(33, 40, 5, "skip"), (33, 5, 9, "empty"), (33, 1, 1, "plain")]
+        for i, (A, T, U, kind) in enumerate(shapes):
+            for dt in (dts if kind == "plain" and T > 1 else dts[:1]):
+                blank = 0 if (i + (dt == "d")) % 2 == 0 else A - 1
+                name = "%s:A%d:T%d:U%d:b%d:%s:%s" % (which, A, T, U, blank, "f64" if dt == "d" else "f32", kind)
+                out.append((name, which, A, T, U, blank, np.float64 if dt == "d" else np.float32, kind))
+    return out
+
+
+def bits_line(cf, case):
+    """Inputs that depend on no libm: multiples of 2^-16 below 1/16, exact in float32 and float64 (the CTC kernels do
+    not need normalised columns); labels uniform over the symbols that are not the blank."""
+    name, which, A, T, U, blank, dt, kind = case
+    rs = np.random.RandomState(zlib.crc32(name.encode()))
+    y = rs.randint(1, 4096, (A, T)) / 65536.0
+    seq = rs.randint(0, A - 1, size=U)
+    seq = (seq + (seq >= blank)).astype(np.int32)
+    if kind == "skip":
+        y[:, (3 * T) // 4] = 0.0
+    with path(which), np.errstate(all="ignore"):
+        cost, grads, skip = cf.ctc_loss_batch([np.asfortranarray(y.astype(dt))], [seq], blank)
+    h = hashlib.sha256(np.float64(cost[0]).tobytes() + np.ascontiguousarray(grads[0].T).tobytes() + bytes([int(skip[0])]))
+    return "%s %d %s %s" % (name, int(skip[0]), float(cost[0]).hex(), h.hexdigest())
+
+
+def bits_recorded():
+    return [l for l in open(BITS_RECORDED).read().splitlines() if l and not l.startswith("#")]
+
+
+def test_outputs_are_bit_identical_to_the_recorded_parent(mods):
+    """Every CTC kernel instantiation's cost, gradient and skip flag, bit for bit (a SHA-256 per case), against
+    tests/data/ctc_bits_parent.txt: the kernels sum in fixed trees and fixed list orders, so a change that only moves
+    code must reproduce every bit, and one that changes a rounding shows up here and not only where a tolerance runs out.
+
+    The file was recorded on an MI355X from a build of commit d852786 (the parent of the change that introduced
+    csrc/ctc_dev.h), through this very code: the Python layer did not change, so that commit's library was loaded into this
+    tree with SCTC_LIB_PATH and `python -m tests.test_gpu_ctc_paths` run twice, in two processes; the two outputs were
+    equal line for line (a case whose two recordings differ would be left out of the file: the test runs the recorded
+    lines only, and tests/test_ctc_plan_cpu.py checks that they still reach every instantiation).  To repeat it: check
+    that commit out, build it, and run the same command with SCTC_LIB_PATH pointing at its libsctc_hip.so.  After a
+    change that is MEANT to change bits, record again from the new build and say so."""
+    cf, _, _ = mods
+    cases = {c[0]: c for c in bits_cases()}
+    recorded = bits_recorded()
+    assert len(recorded) > 150 and all(l.split()[0] in cases for l in recorded)
+    differ = []
+    for want in recorded:
+        got = bits_line(cf, cases[want.split()[0]])
+        if got != want:
+            differ.append((got, want))
+    assert not differ, "%d of %d cases differ, the first: got %r, recorded %r" % (len(differ), len(recorded), differ[0][0], differ[0][1])
+
+
+if __name__ == "__main__":      # the recording (see the test's docstring)
+    import sys
+    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [_root, os.path.join(_root, "stanford-ctc_amd")]
+    import ctc_fast
+    for _case in bits_cases():
+        print(bits_line(ctc_fast, _case), flush=True)

@@ -65,6 +65,7 @@ def main():
             if ref is None:
                 ref = (c, grad.clone())
             out = {"shape": name, "B": B, "T": T, "U": U, "A": A, "path": pname, "wall_ms": min(wall), "gpu_ms": min(gpu),
+                   "gpu_ms_median": float(np.median(gpu)),
                    "algorithmic_GBps_wall": algo / (min(wall) * 1e-3) / 1e9, "algorithmic_GBps_gpu": algo / (min(gpu) * 1e-3) / 1e9,
                    "skipped": int(skip.sum()), "cost0": float(c[0]), "sum_abs_grad": gsum,
                    "max_cost_rel_vs_first_path": float(np.max(np.abs(c - ref[0]) / np.abs(ref[0]))),
