@@ -559,6 +559,69 @@ int sctc_nbest_rank_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_
                           const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
                           const double* first_scores_dev, double* rescored_dev, int32_t* order_dev, void* stream);
 
+/* ---- word-LM scores of label sequences: the word LM as a second pass -----
+ * Added without an ABI version bump (still 6): sctc_word_lm_score_workspace_bytes, sctc_word_lm_score_batch,
+ * sctc_nbest_rank_words_batch. */
+
+#define SCTC_WORD_LM_EOS 1            /* one more term, P(</s> | history); not counted as a word */
+#define SCTC_WORD_LM_NO_FINAL_WORD 2  /* a last token that no space follows is no word: the lexicon search's count */
+
+/* N sequences of CTC symbol ids on the device, as for sctc_lm_score_batch: sequence n is l[0..U) = labels_dev[
+ * label_off[n] .. + U_b[n]); offsets may repeat and may point into the ids of a beam search in place.
+ *   tokens   a token is a maximal run of symbols other than the lexicon's space; leading, trailing and repeated
+ *            spaces make no empty word (str.split()).  Every token is a word, except the last one when no space
+ *            follows it and SCTC_WORD_LM_NO_FINAL_WORD is set.
+ *   word id  walk the lexicon's tree from the root over the token's symbols: if every step exists and a word ends at
+ *            the last node, that word's id; otherwise the token is out of vocabulary (OOV) and gets `unk`.
+ *   term k   the float32 value that the lexicon search adds at the space after word k: bg_prob(previous word, w) of a
+ *            bigram lexicon (previous word of word 0: <s>), P(w | the last order-1 words of <s> and the words before)
+ *            of an n-gram lexicon; the same device routines, the same bits.  Natural log, the word LM's own unit
+ *            (the character LMs' terms are log10).  With SCTC_WORD_LM_EOS one last term, P(</s> | history). */
+typedef struct sctc_word_lm_score_config {
+    int32_t N;                  /* sequences, >= 0 */
+    int32_t A;                  /* symbols incl. the blank 0: the A the lexicon was created with */
+    sctc_lexicon_t lexicon;     /* of sctc_lexicon_create or sctc_lexicon_create_ngram */
+    int32_t unk;                /* word id of <UNK>, or -1: an OOV word then gives status 3 */
+    int32_t end;                /* word id of </s>, or -1 (SCTC_WORD_LM_EOS needs it) */
+    int32_t flags;              /* SCTC_WORD_LM_* */
+    int32_t reserved;           /* not read */
+    const int32_t* U_b;         /* host [N], 0..8191 */
+    const int64_t* label_off;   /* host [N], >= 0 */
+} sctc_word_lm_score_config;
+
+/* *bytes: device workspace of the call: 24 bytes a sequence and an int32 per slot (below), each slice rounded up to
+ * 256 bytes. */
+int sctc_word_lm_score_workspace_bytes(const sctc_word_lm_score_config* cfg, size_t* bytes);
+
+/* Sequence n owns the slots from sum_{q<n} (ceil(U_b[q] / 2) + 1): a row of U symbols has at most ceil(U / 2) words,
+ * and one slot more for </s>.  terms_dev float32 / word_ids_dev int32 [slots] or NULL: term k and the id of word k
+ * (unk for an OOV word, `end` at the </s> term) at slot k of the sequence; the slots past its terms are not written.
+ * sums_dev double [N]: the float64 sum of the sequence's terms, added in word order; no words gives 0.0, or the </s>
+ * term alone.  counts_dev int32 [N][2]: words, OOV words.  status_dev int32 [N]: 0; 2 for a sequence with a label
+ * outside [1, A): sum -inf, counts 0, nothing outside the tables is read; 3 for an OOV word with unk == -1: sum -inf.
+ * Terms and word ids of a sequence whose status is not 0 are not written.
+ * SCTC_ERR_ARG (no device needed): NULL config, lexicon, arrays or outputs, N < 0, A outside 1..256 or not the
+ * lexicon's, unknown flags, unk or end outside -1..words-1, SCTC_WORD_LM_EOS with end == -1, a length outside
+ * 0..8191, a negative offset; SCTC_ERR_WORKSPACE: workspace too small.  N == 0 launches nothing.  One launch, one
+ * wave per sequence; no atomics: deterministic bit for bit.  Allocates no device memory; the descriptors go through
+ * the calling thread's pinned host buffer into the workspace (same remark on stream capture as
+ * sctc_edit_distance_batch). */
+int sctc_word_lm_score_batch(const sctc_word_lm_score_config* cfg, const int32_t* labels_dev, float* terms_dev,
+                             int32_t* word_ids_dev, double* sums_dev, int32_t* counts_dev, int32_t* status_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* sctc_nbest_rank_batch with a word-LM term: word_sums_dev double [B * K], word_counts_dev int32 [B * K][2] and
+ * word_status_dev int32 [B * K] of sctc_word_lm_score_batch over the pairs.  A real hypothesis with align status 0 and
+ * word status 0 scores, left to right in float64 without contraction,
+ *   ((total + alpha * lm) + beta * U) + (word_alpha * word_sum + word_beta * words)
+ * any other -inf (no 0 * -inf is formed).  Order, ties, K_b and first_scores_dev as in sctc_nbest_rank_batch, whose
+ * kernel this instantiates a second time.  SCTC_ERR_ARG as there, and for a NULL word array. */
+int sctc_nbest_rank_words_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_t* U_b, double alpha, double beta,
+                                const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
+                                const double* first_scores_dev, const double* word_sums_dev,
+                                const int32_t* word_counts_dev, const int32_t* word_status_dev, double word_alpha,
+                                double word_beta, double* rescored_dev, int32_t* order_dev, void* stream);
+
 /* ---- CTC loss on a time-major [T, N, C] tensor: what torch.nn.functional.ctc_loss takes (ctc_torch.py) -----
  * Added without an ABI version bump (still 6): sctc_ctc_tnc_probs, sctc_ctc_tnc_empty, sctc_ctc_tnc_grad
  * (DESIGN.md §4.13).

@@ -116,6 +116,25 @@ LM_SCORE_TILE = 32          # csrc/lm_score_plan.h: sequences (recurrent LM) or 
 LM_SCORE_RESIDENT = 512     # resident tiles of a neural LM, each with its own scratch
 NBEST_MAX_K = 256
 
+
+class WordLmScoreConfig(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("A", ctypes.c_int32), ("lexicon", vp), ("unk", ctypes.c_int32),
+                ("end", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("U_b", c_i32p),
+                ("label_off", c_i64p)]
+
+
+WORD_LM_EOS, WORD_LM_NO_FINAL_WORD = 1, 2
+WORD_LM_MAX_U = 8191
+
+
+def word_lm_slots(U_b):
+    """first slot of every sequence's terms / word ids, and the total: ceil(U / 2) words at the most and </s>"""
+    import numpy as np
+    per = (np.asarray(U_b, dtype=np.int64) + 1) // 2 + 1
+    cuts = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    return cuts[:-1], int(cuts[-1])
+
+
 class TncConfig(ctypes.Structure):
     _fields_ = [("T", ctypes.c_int32), ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("dtype", ctypes.c_int32),
                 ("mode", ctypes.c_int32), ("blank", ctypes.c_int32), ("stride_t", ctypes.c_int64),
@@ -189,6 +208,13 @@ PROTOTYPES = {
     "sctc_lm_score_batch": (ctypes.c_int, [ctypes.POINTER(LmScoreConfig), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "sctc_nbest_rank_batch": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p, ctypes.c_double,
                                              ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "sctc_word_lm_score_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(WordLmScoreConfig),
+                                                          ctypes.POINTER(ctypes.c_size_t)]),
+    "sctc_word_lm_score_batch": (ctypes.c_int, [ctypes.POINTER(WordLmScoreConfig), vp, vp, vp, vp, vp, vp, vp,
+                                                ctypes.c_size_t, vp]),
+    "sctc_nbest_rank_words_batch": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p, ctypes.c_double,
+                                                   ctypes.c_double, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double,
+                                                   ctypes.c_double, vp, vp, vp]),
     "sctc_ctc_tnc_probs": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp]),
     "sctc_ctc_tnc_empty": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]),
     "sctc_ctc_tnc_grad": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, vp, vp, vp]),

@@ -33,5 +33,6 @@ struct sctc_lexicon {
     size_t bytes = 0;
     int32_t A = 0, start = 0;
     int32_t order = 0;          // 0: the word-bigram LM of §4.6; 2..5: an n-gram LM of that order
+    int32_t space = 0;          // the word separator the tree was checked against
     int device = -1;
 };

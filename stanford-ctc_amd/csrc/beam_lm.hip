@@ -168,6 +168,7 @@ int sctc_lexicon_create(const int32_t* child_host, const int32_t* word_host, int
     sctc_lexicon* lx = nullptr;
     SCTC_TRY(upload_lexicon(arr, 6, off, &lx));
     point_lexicon(lx, off, nodes, n_words, bg_capacity, A, start_word);
+    lx->space = space;
     *out = lx;
     return SCTC_OK;
 }
@@ -238,6 +239,7 @@ int sctc_lexicon_create_ngram(const int32_t* child_host, const int32_t* word_hos
     sctc_lexicon* lx = nullptr;
     SCTC_TRY(upload_lexicon(arr, 8, off, &lx));
     point_lexicon(lx, off, nodes, n_words, ng_capacity, A, start_word);
+    lx->space = space;
     lx->ng_bo = (float*)(lx->mem + off[6]);
     lx->ng_id = (int32_t*)(lx->mem + off[7]);
     lx->order = order;

@@ -16,7 +16,8 @@
 // rnnlm_tile and nnlm_tile are the routines the searches call (rnnlm_dev.h, nnlm_dev.h): a row is the same function of
 // the prefix here as there, bit for bit.  One small kernel, shared by the three, adds a sequence's terms in position
 // order in float64.  A second entry, sctc_nbest_rank_batch, combines the totals of one forced-alignment launch with the
-// LM sums and ranks each utterance's hypotheses, one wave per utterance, by counting.
+// LM sums and ranks each utterance's hypotheses, one wave per utterance, by counting; sctc_nbest_rank_words_batch is the
+// same kernel instantiated with the word-LM term of word_lm_score.hip (§4.14).
 #include <math.h>
 
 #include <vector>
@@ -258,8 +259,14 @@ struct RankArgs {
     int32_t* order;
     double alpha, beta;
     int32_t B, K;
+    // the word-LM term of sctc_nbest_rank_words_batch (§4.14); not read by the kernel without it
+    const double* wsum;     // [B * K]
+    const int32_t* wcount;  // [B * K][2]: words, OOV words
+    const int32_t* wstatus; // [B * K]
+    double walpha, wbeta;
 };
 
+template <bool WORDS>
 __global__ __launch_bounds__(256) void nbest_rank_kernel(RankArgs p)
 {
 #pragma clang fp contract(off)
@@ -288,6 +295,17 @@ __global__ __launch_bounds__(256) void nbest_rank_kernel(RankArgs p)
             const double t = p.scores[2 * o + 1] + a;
             const double bu = p.beta * (double)p.U[o];
             v = t + bu;
+            if constexpr (WORDS) {
+                // a hypothesis the word LM cannot score is out: no 0 * -inf
+                if (p.wstatus[o] == 0) {
+                    const double wa = p.walpha * p.wsum[o];
+                    const double wb = p.wbeta * (double)p.wcount[2 * o];
+                    const double wt = wa + wb;
+                    v = v + wt;
+                } else {
+                    v = -INFINITY;
+                }
+            }
         }
         s[k] = v;
         p.out[o] = v;
@@ -443,9 +461,10 @@ int sctc_lm_score_batch(const sctc_lm_score_config* cfg, const int32_t* labels_d
     return SCTC_OK;
 }
 
-int sctc_nbest_rank_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_t* U_b, double alpha, double beta,
-                          const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
-                          const double* first_scores_dev, double* rescored_dev, int32_t* order_dev, void* stream)
+// the two rank entries: `a` arrives with the word arrays set or not
+static int rank_launch(bool words, int32_t B, int32_t K, const int32_t* K_b, const int32_t* U_b, double alpha, double beta,
+                       const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
+                       const double* first_scores_dev, double* rescored_dev, int32_t* order_dev, void* stream, RankArgs a)
 {
     SCTC_CHECK_ARG(B >= 0, "nbest_rank: %d utterances", B);
     SCTC_CHECK_ARG(K >= 1 && K <= KMAX, "nbest_rank: %d hypotheses outside 1..%d", K, KMAX);
@@ -465,7 +484,6 @@ int sctc_nbest_rank_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_
     memcpy(pin + B, U_b, (size_t)P * sizeof(int32_t));
     void* pin_dev = nullptr;
     SCTC_HIP_TRY(hipHostGetDevicePointer(&pin_dev, pin, 0));
-    RankArgs a{};
     a.Kb = (const int32_t*)pin_dev;
     a.U = (const int32_t*)pin_dev + B;
     a.scores = scores_dev;
@@ -479,11 +497,37 @@ int sctc_nbest_rank_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_
     a.B = B;
     a.K = K;
     PinnedUploadGuard guard(s, true);
-    hipLaunchKernelGGL(nbest_rank_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, a);
+    if (words) hipLaunchKernelGGL(nbest_rank_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(nbest_rank_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, a);
     SCTC_HIP_TRY(hipGetLastError());
     SCTC_HIP_TRY(stage->uploaded(s));
     guard.done();
     return SCTC_OK;
+}
+
+int sctc_nbest_rank_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_t* U_b, double alpha, double beta,
+                          const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
+                          const double* first_scores_dev, double* rescored_dev, int32_t* order_dev, void* stream)
+{
+    return rank_launch(false, B, K, K_b, U_b, alpha, beta, scores_dev, status_dev, lm_sums_dev, first_scores_dev,
+                       rescored_dev, order_dev, stream, RankArgs{});
+}
+
+int sctc_nbest_rank_words_batch(int32_t B, int32_t K, const int32_t* K_b, const int32_t* U_b, double alpha, double beta,
+                                const double* scores_dev, const int32_t* status_dev, const double* lm_sums_dev,
+                                const double* first_scores_dev, const double* word_sums_dev,
+                                const int32_t* word_counts_dev, const int32_t* word_status_dev, double word_alpha,
+                                double word_beta, double* rescored_dev, int32_t* order_dev, void* stream)
+{
+    SCTC_CHECK_ARG(B <= 0 || (word_sums_dev && word_counts_dev && word_status_dev), "nbest_rank: null word-LM array");
+    RankArgs a{};
+    a.wsum = word_sums_dev;
+    a.wcount = word_counts_dev;
+    a.wstatus = word_status_dev;
+    a.walpha = word_alpha;
+    a.wbeta = word_beta;
+    return rank_launch(true, B, K, K_b, U_b, alpha, beta, scores_dev, status_dev, lm_sums_dev, first_scores_dev,
+                       rescored_dev, order_dev, stream, a);
 }
 
 }  // extern "C"

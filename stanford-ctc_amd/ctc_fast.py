@@ -912,13 +912,19 @@ def lm_sentence_scores(seqs, lm):
     return out
 
 
-def score_sentences(logprobs, seqs, lengths=None, lm=None, alpha=1.0, beta=0.0):
+def score_sentences(logprobs, seqs, lengths=None, lm=None, alpha=1.0, beta=0.0, word_lm=None, word_alpha=1.0,
+                    word_beta=0.0, word_final=True):
     """float64 [B]: the score of label row ``seqs[b]`` under the objective that the character beam
     search maximises, log P_ctc(l) + alpha * sum_i log10 P_LM(l_i | <s>, l_<i) + beta * U: what the
     key of :func:`decode_beam_batch` converges to for prefix l with nothing pruned.
     No end-of-sentence term, as in ``BeamLMDecoder``.  -inf where the row cannot be aligned
     (status != 0 of :func:`align_batch`).  One :func:`align_batch` call; the LM term is computed on
-    the host (:func:`lm_sentence_scores`)."""
+    the host (:func:`lm_sentence_scores`).
+
+    word_lm (a :class:`DecodeLexicon`): adds ``word_alpha * (sum of the word LM's terms) + word_beta * words`` by the
+    rules of :func:`word_lm_sentence_scores` (natural log, no ``</s>`` term); a row the word LM cannot score is -inf.
+    With ``lm=None, beta=0, word_final=False`` this is the objective of :func:`decode_lexicon_beam_batch` with
+    ``alpha=word_alpha, beta=word_beta``."""
     rows = [np.asarray(s).reshape(-1) for s in seqs]
     _, _, _, total, status = align_batch(logprobs, rows, lengths=lengths, total=True)
     score = np.full(len(rows), -np.inf, dtype=np.float64)
@@ -930,6 +936,11 @@ def score_sentences(logprobs, seqs, lengths=None, lm=None, alpha=1.0, beta=0.0):
     lmv = lm_sentence_scores(good, lm) if lm is not None else np.zeros(len(rows))
     for b in np.nonzero(ok)[0]:
         score[b] = total[b] + float(alpha) * lmv[b] + float(beta) * len(rows[b])
+    if word_lm is not None:
+        wsum, wcount, wstatus = word_lm_sentence_scores(good, word_lm, final_word=word_final)
+        for b in np.nonzero(ok)[0]:
+            score[b] = score[b] + (float(word_alpha) * wsum[b] + float(word_beta) * float(wcount[b, 0])) \
+                if wstatus[b] == 0 else -np.inf
     return score
 
 
@@ -1044,7 +1055,149 @@ def lm_perplexity(seqs_of_lm_ids, lm, eos=True):
     return 10.0 ** (-mean), -mean * np.log2(10.0), n
 
 
-def rescore_nbest(logprobs, hyps, lengths=None, lm=None, alpha=1.0, beta=0.0, device=False, scores=None, K_b=None):
+# ---- the word LM as a second pass ----
+
+def _word_lexicon(lexicon, what):
+    if not isinstance(lexicon, DecodeLexicon):
+        raise ValueError("%s: the word LM must be a ctc_fast.DecodeLexicon" % what)
+    return lexicon
+
+
+def word_lm_sentence_scores(seqs, lexicon, eos=False, final_word=True):
+    """The host route of :func:`word_lm_score_batch` (no GPU): (sums float64 [N], counts int32 [N, 2], status int32
+    [N]) of label rows under the word LM of ``lexicon`` -- a :class:`DecodeLexicon`, or anything with its ``tree``
+    (a ``PrefixTree``), ``lm`` (a ``decoder.lm.LM`` or a ``decoder.ngram_lm.NgramLM``) and ``A``.
+
+    A token is a maximal run of symbols other than the tree's space (``str.split()``); every token is a word, except
+    the last one when no space follows it and ``final_word`` is False (the lexicon search's count).  A token's word id
+    is what the tree gives at the end of its spelling; a token that leaves the tree, or ends at no word, is OOV and
+    scores as ``lm.unk``.  Term k is ``bg_prob(previous word, w)`` / ``prob(<s> + the words before, w)``, float32,
+    NATURAL log; ``eos`` adds ``P(</s> | history)``, which is no word.  The sum is float64 in word order.  counts:
+    (words, OOV words).  status: 0; 2 a symbol outside 1..A-1 (sum -inf, counts 0); 3 an OOV word and the LM has no
+    ``<UNK>`` (sum -inf)."""
+    from decoder import ngram_lm
+    tree, lm, A = lexicon.tree, lexicon.lm, int(lexicon.A)
+    ngram = isinstance(lm, ngram_lm.NgramLM)
+    space = int(tree.space)
+    N = len(seqs)
+    sums = np.zeros(N, dtype=np.float64)
+    counts = np.zeros((N, 2), dtype=np.int32)
+    status = np.zeros(N, dtype=np.int32)
+    for n, s in enumerate(seqs):
+        row = [int(c) for c in np.asarray(s).reshape(-1)]
+        if any(not 1 <= c < A for c in row):
+            status[n], sums[n] = 2, -np.inf
+            continue
+        tokens, cur = [], []
+        for c in row:
+            if c == space:
+                if cur:
+                    tokens.append(cur)
+                cur = []
+            else:
+                cur.append(c)
+        if cur and final_word:
+            tokens.append(cur)
+        ids = []
+        for tok in tokens:
+            node = tree.root
+            for c in tok:
+                node = node.children[c] if node.children is not None and c in node.children else None
+                if node is None:
+                    break
+            known = node is not None and node.isWord
+            counts[n, 1] += 0 if known else 1
+            ids.append(int(node.id) if known else lm.unk)
+        counts[n, 0] = len(ids)
+        if any(w is None for w in ids):
+            status[n], sums[n] = 3, -np.inf
+            continue
+        hist = [int(lm.start)]
+        total = 0.0
+        for w in ids + ([int(lm.end)] if eos else []):
+            total += float(lm.prob(hist, w) if ngram else lm.bg_prob(hist[-1], w))
+            hist.append(w)
+        sums[n] = total
+    return sums, counts, status
+
+
+def _word_lm_launch(lexicon, labels_dev, U_b, loff, want_terms, want_words, eos, final_word, what):
+    """sctc_word_lm_score_batch on device labels: (sums float64 [N], counts int32 [N, 2], status int32 [N], terms
+    float32 [slots] or None, word ids int32 [slots] or None), device tensors"""
+    torch = _sctc.require_gpu()
+    N = int(U_b.shape[0])
+    lm = lexicon.lm
+    flags = (_sctc.WORD_LM_EOS if eos else 0) | (0 if final_word else _sctc.WORD_LM_NO_FINAL_WORD)
+    cfg = _sctc.WordLmScoreConfig(N, int(lexicon.A), lexicon.handle, -1 if lm.unk is None else int(lm.unk),
+                                  -1 if lm.end is None else int(lm.end), flags, 0, _sctc.i32(U_b), _sctc.i64(loff))
+    L = _sctc.lib()
+    nbytes = ctypes.c_size_t(0)
+    _sctc.check(L.sctc_word_lm_score_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)), what)
+    device = labels_dev.device
+    slots = _sctc.word_lm_slots(U_b)[1]
+    sums = torch.empty(N, dtype=torch.float64, device=device)
+    counts = torch.empty((N, 2), dtype=torch.int32, device=device)
+    status = torch.empty(N, dtype=torch.int32, device=device)
+    terms = torch.zeros(max(1, slots), dtype=torch.float32, device=device) if want_terms else None
+    wids = torch.full((max(1, slots),), -1, dtype=torch.int32, device=device) if want_words else None
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=device)
+    rc = L.sctc_word_lm_score_batch(ctypes.byref(cfg), labels_dev.data_ptr(), terms.data_ptr() if want_terms else None,
+                                    wids.data_ptr() if want_words else None, sums.data_ptr(), counts.data_ptr(),
+                                    status.data_ptr(), ws.data_ptr(), nbytes.value, _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    return sums, counts, status, terms, wids
+
+
+def word_lm_score_batch(seqs, lexicon, terms=False, words=False, eos=False, final_word=True, device=False):
+    """(sums float64 [N], counts int32 [N, 2], status int32 [N]) of label rows under the word LM of ``lexicon`` (a
+    :class:`DecodeLexicon`, bigram or n-gram), in one launch on the device: what
+    :func:`word_lm_sentence_scores` returns, bit for bit -- its docstring has the rules.  The terms are NATURAL-log
+    values, the float32 numbers that :func:`decode_lexicon_beam_batch` adds at the space after a word.
+
+    ``seqs`` as for :func:`lm_score_batch`: a list of CTC symbol-id sequences, or a device triple (ids int32 tensor,
+    U, offsets) read in place.  ``terms=True`` / ``words=True`` append the float32 term and the word id (``unk`` for
+    an OOV word, ``end`` at the ``</s>`` term) of every word: lists of arrays (empty for a row whose status is not 0),
+    or with ``device=True`` flat tensors in which sequence n starts at slot ``sum((U[:n] + 1) // 2 + 1)``.
+    ``device=True``: nothing is read back."""
+    what = "word_lm_score_batch"
+    _word_lexicon(lexicon, what)
+    if eos and lexicon.lm.end is None:
+        raise ValueError("%s: the LM has no </s>" % what)
+    labels, U_b, loff = _score_seqs(seqs, what, _sctc.WORD_LM_MAX_U)
+    sums, counts, status, tv, wv = _word_lm_launch(lexicon, labels, U_b, loff, bool(terms), bool(words), eos,
+                                                   final_word, what)
+    extra = [v for v, want in ((tv, terms), (wv, words)) if want]
+    if device:
+        return (sums, counts, status) + tuple(extra)
+    sums, counts, status = sums.cpu().numpy(), counts.cpu().numpy(), status.cpu().numpy()
+    first = _sctc.word_lm_slots(U_b)[0]
+    n_terms = np.where(status == 0, counts[:, 0] + (1 if eos else 0), 0)
+    lists = []
+    for v in extra:
+        flat = v.cpu().numpy()
+        lists.append([flat[first[n]:first[n] + n_terms[n]].copy() for n in range(U_b.shape[0])])
+    return (sums, counts, status) + tuple(lists)
+
+
+def word_lm_perplexity(sentences_as_label_rows, lexicon, eos=True):
+    """(perplexity, n_terms, n_oov) of sentences given as rows of CTC symbols under the word LM of ``lexicon``:
+    ``e ** (-sum of the natural-log terms / n_terms)``, n_terms the words plus, with ``eos``, one ``</s>`` a
+    sentence; n_oov the words scored as ``<UNK>``.  One :func:`word_lm_score_batch` call.  ValueError for a row the
+    LM cannot score, and when there is nothing to score."""
+    what = "word_lm_perplexity"
+    rows = [np.asarray(s).reshape(-1) for s in sentences_as_label_rows]
+    sums, counts, status = word_lm_score_batch(rows, lexicon, eos=eos)
+    if (status != 0).any():
+        raise ValueError("%s: sentence %d cannot be scored (status %d)"
+                         % (what, int(np.nonzero(status)[0][0]), int(status[np.nonzero(status)[0][0]])))
+    n = int(counts[:, 0].sum()) + (len(rows) if eos else 0)
+    if n == 0:
+        raise ValueError("%s: nothing to score" % what)
+    return float(np.exp(-float(sums.sum()) / n)), n, int(counts[:, 1].sum())
+
+
+def rescore_nbest(logprobs, hyps, lengths=None, lm=None, alpha=1.0, beta=0.0, device=False, scores=None, K_b=None,
+                  word_lm=None, word_alpha=1.0, word_beta=0.0, word_eos=False, word_final=True):
     """Second pass over n-best lists: every hypothesis gets the score that
     :func:`score_sentences` gives it, log P_ctc(l) + alpha * sum_i log10 P_LM(l_i | <s>, l_<i) + beta * U with the
     full CTC sum, and every utterance's hypotheses are ranked by it -- one forced-alignment launch, one LM-score
@@ -1057,7 +1210,14 @@ def rescore_nbest(logprobs, hyps, lengths=None, lm=None, alpha=1.0, beta=0.0, de
     device route has them) or by ``K_b`` (int [B]: the leading ranks that are real), stay last and score -inf.
     Returns (order int32 [B, K]: hypothesis indices by descending score, ties to the lower first-pass rank;
     rescored float64 [B, K]: by first-pass rank, -inf where the hypothesis cannot be aligned); device tensors
-    with ``device=True``."""
+    with ``device=True``.
+
+    word_lm (a :class:`DecodeLexicon`): one :func:`word_lm_score_batch` launch more over the same labels, and the
+    score becomes ``((log P_ctc + alpha * lm) + beta * U) + (word_alpha * word_sum + word_beta * words)`` -- the
+    character LM finds the hypotheses, the word LM orders them.  ``word_alpha`` weighs NATURAL-log
+    terms (the word LM's unit, as ``alpha`` of :func:`decode_lexicon_beam_batch`); ``alpha`` weighs log10 terms.
+    ``word_eos`` / ``word_final`` as ``eos`` / ``final_word`` there.  A hypothesis the word LM cannot score (an OOV
+    word under an LM without ``<UNK>``) is -inf."""
     what = "rescore_nbest"
     arrs, src, A, T_b, dt, dtype = _decode_inputs(logprobs, lengths, what)
     B = len(T_b)
@@ -1066,6 +1226,10 @@ def rescore_nbest(logprobs, hyps, lengths=None, lm=None, alpha=1.0, beta=0.0, de
         _lm_kind(lm, what)
         if lm.sym_words.shape[0] < A:
             raise ValueError("%s: the LM maps %d symbols, the input has %d" % (what, lm.sym_words.shape[0], A))
+    if word_lm is not None:
+        _word_lexicon(word_lm, what)
+        if word_lm.A != A:
+            raise ValueError("%s: the lexicon was built for %d symbols, the input has %d" % (what, word_lm.A, A))
     Tb = np.ascontiguousarray(T_b, dtype=np.int32)
     foff = np.concatenate([[0], np.cumsum(Tb)[:-1]]).astype(np.int64) if B else np.zeros(0, np.int64)
     first = None
@@ -1134,10 +1298,17 @@ def rescore_nbest(logprobs, hyps, lengths=None, lm=None, alpha=1.0, beta=0.0, de
     # ---- one rank launch ----
     rescored = torch.empty((B, K), dtype=torch.float64, device=device_)
     order = torch.empty((B, K), dtype=torch.int32, device=device_)
-    rc = L.sctc_nbest_rank_batch(B, K, _sctc.i32(Kb), _sctc.i32(U_b), float(alpha), float(beta), a_scores.data_ptr(),
-                                 a_status.data_ptr(), lm_sums.data_ptr() if lm_sums is not None else None,
-                                 first.data_ptr() if first is not None else None, rescored.data_ptr(),
-                                 order.data_ptr(), _sctc.current_stream_ptr())
+    head = (B, K, _sctc.i32(Kb), _sctc.i32(U_b), float(alpha), float(beta), a_scores.data_ptr(), a_status.data_ptr(),
+            lm_sums.data_ptr() if lm_sums is not None else None, first.data_ptr() if first is not None else None)
+    tail = (rescored.data_ptr(), order.data_ptr(), _sctc.current_stream_ptr())
+    if word_lm is not None and P:
+        # ---- one word-LM call, and the rank entry that takes its sums ----
+        w_sums, w_counts, w_status, _, _ = _word_lm_launch(word_lm, labels, U_b, loff, False, False, word_eos,
+                                                           word_final, what)
+        rc = L.sctc_nbest_rank_words_batch(*(head + (w_sums.data_ptr(), w_counts.data_ptr(), w_status.data_ptr(),
+                                                     float(word_alpha), float(word_beta)) + tail))
+    else:
+        rc = L.sctc_nbest_rank_batch(*(head + tail))
     _sctc.check(rc, what)
     if device:
         return order, rescored

@@ -145,7 +145,8 @@ class BeamLMDecoder(DecoderBase):
         return self._dev[key][0]
 
     def decode_batch(self, probs_list, beam=40, alpha=1.0, beta=0.0, nbest=1, rescore_lm=None, rescore_alpha=None,
-                     rescore_beta=None, rescore_nbest=None):
+                     rescore_beta=None, rescore_nbest=None, rescore_word_lm=None, rescore_word_alpha=1.0,
+                     rescore_word_beta=0.0):
         """[(hyp, score)] for a list of (A, T) log-probability arrays, one launch; with nbest > 1 a list
         of nbest (hyp, score) per utterance, best first (ranks beyond the beam: '', -inf).
 
@@ -154,7 +155,12 @@ class BeamLMDecoder(DecoderBase):
         utterance (default: all ``nbest``) by log P_ctc + rescore_alpha * log10 P_LM + rescore_beta * length under that
         LM (the weights default to the first pass's) and returns them in the new order with the new scores; the
         ranks it leaves alone follow with their first-pass scores.  ``self.rescore_changed`` then says, per
-        utterance, whether the 1-best changed."""
+        utterance, whether the 1-best changed.
+
+        ``rescore_word_lm`` (a ctc_fast.DecodeLexicon), alone or with ``rescore_lm``: the second pass adds
+        rescore_word_alpha * (natural-log word-LM score) + rescore_word_beta * words.  Alone, the
+        character-LM term of the second pass is left out; its length bonus rescore_beta * length (default: the first
+        pass's ``beta``) stays -- pass ``rescore_beta=0.0`` for log P_ctc and the word term only."""
         if int(beam) < 0:
             raise OverflowError("can't convert negative value to unsigned int")
         for p in probs_list:
@@ -163,7 +169,7 @@ class BeamLMDecoder(DecoderBase):
         A = probs_list[0].shape[0]
         ids, scores = ctc_fast.decode_beam_batch(probs_list, beam=beam, alpha=alpha, beta=beta,
                                                  lm=self._device_lm(A), nbest=nbest)
-        if rescore_lm is not None:
+        if rescore_lm is not None or rescore_word_lm is not None:
             rows = ids if nbest > 1 else [[h] for h in ids]
             first = np.array(scores, dtype=np.float64).reshape(len(rows), nbest)
             seen = first.copy()
@@ -171,9 +177,12 @@ class BeamLMDecoder(DecoderBase):
                 if not 1 <= int(rescore_nbest) <= nbest:
                     raise ValueError("decode_batch: rescore_nbest outside 1..nbest")
                 seen[:, int(rescore_nbest):] = -np.inf
-            order, res = ctc_fast.rescore_nbest(probs_list, rows, lm=self._rescore_lm(rescore_lm, A),
+            order, res = ctc_fast.rescore_nbest(probs_list, rows,
+                                                lm=self._rescore_lm(rescore_lm, A) if rescore_lm is not None else None,
                                                 alpha=alpha if rescore_alpha is None else rescore_alpha,
-                                                beta=beta if rescore_beta is None else rescore_beta, scores=seen)
+                                                beta=beta if rescore_beta is None else rescore_beta, scores=seen,
+                                                word_lm=rescore_word_lm, word_alpha=rescore_word_alpha,
+                                                word_beta=rescore_word_beta)
             self.rescore_changed = [int(o[0]) != 0 for o in order]
             out = [[(self._string(row[k]), float(res[b, k]) if seen[b, k] > -np.inf else float(first[b, k])) for k in o]
                    for b, (row, o) in enumerate(zip(rows, order))]

@@ -22,7 +22,7 @@ against the alignment, the naming of editDistance.py) and adds a line of totals 
 ``--nbest-oracle K`` (character method) decodes K hypotheses per utterance and prints the CER of
 the best of them next to the 1-best CER.
 
-``--ref-scores FILE`` (character method) writes ``key hypscore refscore`` per utterance with a
+``--ref-scores FILE`` writes ``key hypscore refscore`` per utterance with a
 transcript: the transcript scored under the objective the search maximises
 (ctc_fast.score_sentences; the refScore that the reference's decoder_utils.py:68-70
 left open), and adds a line that counts the search errors (refscore > hypscore) and the transcripts
@@ -34,6 +34,13 @@ the hypothesis (ctc_fast.align_batch): words are the runs of labels between ``--
 second pass (ctc_fast.rescore_nbest): the K best hypotheses of the search are re-ranked under the
 LM of FILE (ARPA, or the .npz of a neural LM) with the full CTC sum; the hypothesis file and the CER are those of the
 re-ranked 1-best, and the summary says how many utterances changed their 1-best.
+``--rescore-word-lm ARPA --rescore-words WORDLIST [--rescore-word-lm-order N --rescore-word-alpha --rescore-word-beta]``,
+alone or next to ``--rescore-lm``, puts a word LM into that second pass: the character LM finds the
+hypotheses, the word LM orders them; a word outside WORDLIST scores as ``<UNK>``.  The word LM's score is in natural
+log, so its weight means what ``--alpha`` means for ``--method bg``.
+
+With ``--method bg``, ``--ref-scores FILE`` scores the transcript under the word search's objective: log P_ctc +
+alpha * (word-LM terms of the words a space follows) + beta * (those words).
 """
 import argparse
 import os
@@ -197,11 +204,19 @@ def decode_bg(a, ll):
     lex = ctc_fast.DecodeLexicon(a.words, chars, a.word_lm, a.space, specials=a.specials, order=a.word_lm_order)
     keys = sorted(ll)
     errs = n_ref = werrs = n_words = 0
-    with open(a.out, "w") as out, ErrorLog(a.errors) as log:
+    with open(a.out, "w") as out, ErrorLog(a.errors) as log, RefScoreLog(a.ref_scores) as ref_log:
         for g in range(0, len(keys), a.batch):
             ks = keys[g:g + a.batch]
             hyps, scores = ctc_fast.decode_lexicon_beam_batch([np.asarray(ll[k]) for k in ks], lexicon=lex,
                                                               beam=a.beam, alpha=a.alpha, beta=a.beta)
+            if ref_log.f:       # the transcripts under the search's objective: words finished, no character LM
+                idx = [i for i, k in enumerate(ks) if k in alis]
+                if idx:
+                    ref_ids = [[chars.get(t, -1) for t in alis[ks[i]]] for i in idx]
+                    ref_scores = ctc_fast.score_sentences([np.asarray(ll[ks[i]]) for i in idx], ref_ids, word_lm=lex,
+                                                          word_alpha=a.alpha, word_beta=a.beta, word_final=False)
+                    for i, rs in zip(idx, ref_scores):
+                        ref_log.add(ks[i], scores[i], rs)
             scored, refs, cand = [], [], []
             for k, ids, score in zip(ks, hyps, scores):
                 toks = decoder_utils.int_to_char(ids, chars)
@@ -224,6 +239,7 @@ def decode_bg(a, ll):
     print("decoded %d utterances, CER %.4f (%d / %d), WER %.4f (%d / %d)"
           % (len(keys), cer, errs, n_ref, wer, werrs, n_words))
     log.summary()
+    ref_log.summary()
     return cer, wer
 
 
@@ -252,7 +268,7 @@ def main(argv=None):
                     help="also report the CER of the best of K hypotheses per utterance (character method, K <= beam)")
     ap.add_argument("--ref-scores", metavar="FILE",
                     help="write `key hypscore refscore` per utterance with a transcript: the transcript scored under "
-                         "the search's own objective (character method)")
+                         "the search's own objective (either method)")
     ap.add_argument("--ctm", metavar="FILE",
                     help="write a CTM with the time of every word of the 1-best hypotheses, from their forced "
                          "alignment (character method)")
@@ -262,19 +278,30 @@ def main(argv=None):
     ap.add_argument("--rescore-nbest", type=int, default=0, metavar="K", help="hypotheses re-ranked per utterance, K <= beam")
     ap.add_argument("--rescore-alpha", type=float, default=None, help="LM weight of the second pass (default --alpha)")
     ap.add_argument("--rescore-beta", type=float, default=None, help="length bonus of the second pass (default --beta)")
+    ap.add_argument("--rescore-word-lm", metavar="ARPA",
+                    help="second pass: add a word LM's score over the words of the --rescore-nbest best hypotheses, "
+                         "alone or with --rescore-lm; needs --rescore-words (character method)")
+    ap.add_argument("--rescore-words", metavar="WORDLIST", help="word list of --rescore-word-lm, one per line")
+    ap.add_argument("--rescore-word-lm-order", type=int, default=2, help="order 2..5 at which --rescore-word-lm is read")
+    ap.add_argument("--rescore-word-alpha", type=float, default=1.0,
+                    help="weight of the word LM's natural-log score in the second pass (default 1)")
+    ap.add_argument("--rescore-word-beta", type=float, default=0.0, help="bonus per word of the second pass (default 0)")
     a = ap.parse_args(argv)
     K = a.nbest_oracle
     if K and a.method == "bg":
         ap.error("--nbest-oracle is for the character method")
-    if (a.ref_scores or a.ctm) and a.method == "bg":
-        ap.error("--ref-scores and --ctm are for the character method")
+    if a.ctm and a.method == "bg":
+        ap.error("--ctm is for the character method")
     if K and not 1 <= K <= a.beam:
         ap.error("--nbest-oracle K needs 1 <= K <= beam")
     Kr = a.rescore_nbest
-    if (a.rescore_lm or Kr) and a.method == "bg":
-        ap.error("--rescore-lm is for the character method")
-    if bool(a.rescore_lm) != bool(Kr) or (Kr and not 1 <= Kr <= a.beam):
-        ap.error("--rescore-lm FILE needs --rescore-nbest K with 1 <= K <= beam, and the other way round")
+    if (a.rescore_lm or a.rescore_word_lm or Kr) and a.method == "bg":
+        ap.error("--rescore-lm and --rescore-word-lm are for the character method")
+    if bool(a.rescore_word_lm) != bool(a.rescore_words):
+        ap.error("--rescore-word-lm ARPA needs --rescore-words WORDLIST, and the other way round")
+    if bool(a.rescore_lm or a.rescore_word_lm) != bool(Kr) or (Kr and not 1 <= Kr <= a.beam):
+        ap.error("--rescore-lm FILE / --rescore-word-lm ARPA need --rescore-nbest K with 1 <= K <= beam, and the other "
+                 "way round")
     with open(a.likelihoods, "rb") as f:
         ll = pickle.load(f)
     if a.method == "bg":
@@ -287,6 +314,11 @@ def main(argv=None):
     dec = decoder.BeamLMDecoder()
     dec.load_chars(a.chars)
     dec.load_lm(a.lm)
+    word_lex = None
+    if a.rescore_word_lm:
+        word_lex = ctc_fast.DecodeLexicon(a.rescore_words, dec.char_int_map, a.rescore_word_lm, a.space,
+                                          specials=a.specials, A=np.asarray(ll[sorted(ll)[0]]).shape[0] if ll else None,
+                                          order=a.rescore_word_lm_order)
     keys = sorted(ll)
     errs = n_ref = oracle_errs = n_changed = 0
     space_id = dec.char_int_map.get(a.space)
@@ -297,7 +329,9 @@ def main(argv=None):
             probs = [np.asfortranarray(ll[k], dtype=np.float64) for k in ks]
             if Kr:
                 res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, Kr), rescore_lm=a.rescore_lm,
-                                       rescore_alpha=a.rescore_alpha, rescore_beta=a.rescore_beta, rescore_nbest=Kr)
+                                       rescore_alpha=a.rescore_alpha, rescore_beta=a.rescore_beta, rescore_nbest=Kr,
+                                       rescore_word_lm=word_lex, rescore_word_alpha=a.rescore_word_alpha,
+                                       rescore_word_beta=a.rescore_word_beta)
                 n_changed += sum(dec.rescore_changed)
             else:
                 res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, 1))
