@@ -622,6 +622,108 @@ int sctc_nbest_rank_words_batch(int32_t B, int32_t K, const int32_t* K_b, const 
                                 const int32_t* word_counts_dev, const int32_t* word_status_dev, double word_alpha,
                                 double word_beta, double* rescored_dev, int32_t* order_dev, void* stream);
 
+/* ---- word interning, minimum Bayes risk selection and word confidences over n-best lists -----
+ * Added without an ABI version bump (still 6): sctc_intern_words_workspace_bytes, sctc_intern_words_batch,
+ * sctc_nbest_mbr_workspace_bytes, sctc_nbest_mbr_batch. */
+
+/* N rows of CTC symbol ids on the device, as for sctc_lm_score_batch: row n is l[0..U) = labels_dev[label_off[n] .. +
+ * U_b[n]); offsets may repeat and may point into the ids of a beam search in place.  group_off cuts the rows into G
+ * groups of consecutive rows: group g is rows group_off[g] .. group_off[g + 1] - 1.
+ *   tokens   a token is a maximal run of symbols other than `space`; leading, trailing and repeated spaces make no
+ *            empty word (str.split(), the rule of sctc_word_lm_score_batch).
+ *   ids      number the tokens of a group 0..W-1 in (row, position) order.  The id of token t is the smallest t' <= t
+ *            whose token is the same run of symbols: same length, same symbols.  Two tokens of a group have the same id
+ *            exactly when they are the same word; no lexicon is involved and a hash never merges two words. */
+typedef struct sctc_intern_config {
+    int32_t N;                  /* rows, >= 0 */
+    int32_t G;                  /* groups, >= 0 */
+    int32_t A;                  /* symbols incl. the blank 0, 1..256 */
+    int32_t space;              /* the space symbol, in [1, A) */
+    const int32_t* U_b;         /* host [N], 0..4095 */
+    const int64_t* label_off;   /* host [N], >= 0 */
+    const int32_t* group_off;   /* host [G + 1], from 0 to N, never decreasing */
+} sctc_intern_config;
+
+/* *bytes: device workspace of the call: 32 bytes a row, 8 bytes a group, 4 bytes a row, 24 bytes a word slot and the
+ * groups' hash tables (4 bytes an entry, a power of two of at least twice the group's slots), each slice rounded up to
+ * 256 bytes. */
+int sctc_intern_words_workspace_bytes(const sctc_intern_config* cfg, size_t* bytes);
+
+/* Row n owns the slots from sum_{q<n} ceil(U_b[q] / 2): a row of U symbols has at most ceil(U / 2) words.
+ * word_ids_dev int32 [slots]: the id of word k of the row at its slot k; the slots past its words are not written.
+ * counts_dev int32 [N]: the words of the row.  status_dev int32 [N]: 0, or 2 for a row with a label outside [1, A):
+ * such a row has count 0, none of its slots is written and nothing outside the row is read.
+ * SCTC_ERR_ARG (no device needed): NULL config, arrays or outputs, N < 0, G < 0, A outside 1..256, space outside
+ * [1, A), a length outside 0..4095, a negative offset, a group_off that decreases or does not run from 0 to N;
+ * SCTC_ERR_WORKSPACE: workspace too small.  N == 0 launches nothing.  The insertion uses atomics on the group's
+ * table, of which only an order-independent minimum is kept: the ids are the same bit for bit from run to run.
+ * Allocates no device memory; the descriptors go through the calling thread's pinned host buffer into the workspace:
+ * a call waits for the previous call of the same thread to have read its descriptors, so it cannot be recorded into a
+ * stream capture (hipGraph), as sctc_edit_distance_batch. */
+int sctc_intern_words_batch(const sctc_intern_config* cfg, const int32_t* labels_dev, int32_t* word_ids_dev,
+                            int32_t* counts_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
+                            void* stream);
+
+#define SCTC_MBR_CHARS 0  /* the unit of the edit distance is the symbol */
+#define SCTC_MBR_WORDS 1  /* the word: the K rows of an utterance are interned as one group */
+#define SCTC_MBR_CONF 1   /* also the confidence of every unit of the chosen hypothesis */
+#define SCTC_MBR_DIST 2   /* keep the pairwise distances as an output */
+
+/* B utterances x K hypotheses (K <= 256), pair (b, k) at b * K + k, the rows as for sctc_nbest_rank_batch.
+ * Hypothesis k of utterance b is REAL when k < K_b[b] and scores_dev[b * K + k] is finite.  In word unit a real row
+ * with a label outside [1, A) counts as a row without words. */
+typedef struct sctc_mbr_config {
+    int32_t B;                  /* utterances, >= 0 */
+    int32_t K;                  /* hypotheses per utterance, 1..256 */
+    int32_t unit;               /* SCTC_MBR_CHARS | SCTC_MBR_WORDS */
+    int32_t flags;              /* 0 | SCTC_MBR_CONF | SCTC_MBR_DIST */
+    int32_t A;                  /* symbols incl. the blank 0, 1..256 */
+    int32_t space;              /* the space symbol, in [1, A); read in word unit only */
+    double scale;               /* finite, >= 0: multiplies the score differences */
+    const int32_t* K_b;         /* host [B], 0..K */
+    const int32_t* U_b;         /* host [B * K], 0..4095 */
+    const int64_t* label_off;   /* host [B * K], >= 0 */
+} sctc_mbr_config;
+
+/* *bytes: device workspace of the call (csrc/nbest_mbr_plan.h has the slices): the O(B * K) descriptors, in word unit
+ * the interning's workspace and ids, the B * K * K int32 distances unless SCTC_MBR_DIST, with SCTC_MBR_CONF the paths,
+ * match flags and the operation tables that do not fit on chip. */
+int sctc_nbest_mbr_workspace_bytes(const sctc_mbr_config* cfg, size_t* bytes);
+
+/* scores_dev double [B][K]: the rescored values of sctc_nbest_rank_batch, or the first pass's.  order_dev int32
+ * [B][K]: the ranking of sctc_nbest_rank_batch, or NULL.
+ *   D        dist_dev int32 [B][K][K] (with SCTC_MBR_DIST; otherwise NULL and D lives in the workspace): D[b][k][j] is
+ *            the edit distance (the table of sctc_edit_distance_batch) between hypotheses k and j in the unit, 0 on the
+ *            diagonal, -1 where k or j is not real.  One wave per unordered pair of real hypotheses; the host passes
+ *            no descriptor per pair.
+ *   weights  s_max = the maximum score of the real hypotheses; w_k = exp(scale * (s_k - s_max)), and exactly 1.0
+ *            where s_k == s_max; Z = sum_k w_k over the real ranks in ascending k.  All float64, no contraction.
+ *   post_dev double [B][K]: w_k / Z, 0 for a rank that is not real.
+ *   risk_dev double [B][K]: (sum_j w_j * D[b][k][j], ascending j over the real ranks) / Z, +inf for a rank that is
+ *            not real.
+ *   best_dev int32 [B]: the real rank of least risk; ties go to the hypothesis that comes first in order_dev[b], with
+ *            order_dev == NULL to the lower k; -1 without a real hypothesis.
+ *   mbr_order_dev int32 [B][K]: the ranks by ascending risk under the same tie rule; the ranks that are not real come
+ *            last, in their original order.
+ * With SCTC_MBR_CONF: utterance b owns the slots from sum_{q<b} max_{k<K_b[q]} n_{q,k} of conf_dev (double), n the
+ * host's bound on the unit count: U_b in character unit, ceil(U_b / 2) in word unit.  For every real j the chosen
+ * hypothesis (a) is aligned with hypothesis j (b) by the path of sctc_edit_distance_batch (the first of MATCH / UP /
+ * LEFT / SUB, the leftover rule); match_j[i] = 1 where the path has MATCH at unit i of a, and match_best[i] = 1.
+ *   conf[i] = (sum_j w_j * match_j[i], ascending j over the real ranks) / Z;  conf_len_dev int32 [B]: the unit count
+ * of the chosen hypothesis, 0 without one.  Slots past conf_len are not written.  The chosen index is read on the
+ * device.  Without the flag both pointers are NULL.
+ * SCTC_ERR_ARG (no device needed): NULL config, arrays or outputs, B < 0, K outside 1..256, unknown unit or flags,
+ * K_b outside [0, K], a length outside 0..4095, a negative offset, A outside 1..256, space outside [1, A) in word
+ * unit, a scale that is not finite or is < 0; SCTC_ERR_WORKSPACE: workspace too small.  B == 0 launches nothing.
+ * Apart from the interning's table (see there) no atomics; deterministic bit for bit.  Allocates no device memory;
+ * the descriptors go through the calling thread's pinned host buffer into the workspace: a call waits for the
+ * previous call of the same thread to have read its descriptors, so it cannot be recorded into a stream capture
+ * (hipGraph), as sctc_edit_distance_batch. */
+int sctc_nbest_mbr_batch(const sctc_mbr_config* cfg, const int32_t* labels_dev, const double* scores_dev,
+                         const int32_t* order_dev, double* post_dev, double* risk_dev, int32_t* best_dev,
+                         int32_t* mbr_order_dev, int32_t* dist_dev, double* conf_dev, int32_t* conf_len_dev,
+                         void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- CTC loss on a time-major [T, N, C] tensor: what torch.nn.functional.ctc_loss takes (ctc_torch.py) -----
  * Added without an ABI version bump (still 6): sctc_ctc_tnc_probs, sctc_ctc_tnc_empty, sctc_ctc_tnc_grad
  * (DESIGN.md §4.13).

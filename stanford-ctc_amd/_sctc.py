@@ -135,6 +135,30 @@ def word_lm_slots(U_b):
     return cuts[:-1], int(cuts[-1])
 
 
+class InternConfig(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("G", ctypes.c_int32), ("A", ctypes.c_int32), ("space", ctypes.c_int32),
+                ("U_b", c_i32p), ("label_off", c_i64p), ("group_off", c_i32p)]
+
+
+class MbrConfig(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("K", ctypes.c_int32), ("unit", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("A", ctypes.c_int32), ("space", ctypes.c_int32), ("scale", ctypes.c_double), ("K_b", c_i32p),
+                ("U_b", c_i32p), ("label_off", c_i64p)]
+
+
+MBR_CHARS, MBR_WORDS = 0, 1
+MBR_CONF, MBR_DIST = 1, 2
+MBR_MAX_U = ALIGN_MAX_U
+
+
+def intern_slots(U_b):
+    """first word slot of every row, and the total: a row of U symbols has ceil(U / 2) words at the most"""
+    import numpy as np
+    per = (np.asarray(U_b, dtype=np.int64) + 1) // 2
+    cuts = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    return cuts[:-1], int(cuts[-1])
+
+
 class TncConfig(ctypes.Structure):
     _fields_ = [("T", ctypes.c_int32), ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("dtype", ctypes.c_int32),
                 ("mode", ctypes.c_int32), ("blank", ctypes.c_int32), ("stride_t", ctypes.c_int64),
@@ -215,6 +239,11 @@ PROTOTYPES = {
     "sctc_nbest_rank_words_batch": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p, ctypes.c_double,
                                                    ctypes.c_double, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double,
                                                    ctypes.c_double, vp, vp, vp]),
+    "sctc_intern_words_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(InternConfig), ctypes.POINTER(ctypes.c_size_t)]),
+    "sctc_intern_words_batch": (ctypes.c_int, [ctypes.POINTER(InternConfig), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "sctc_nbest_mbr_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(MbrConfig), ctypes.POINTER(ctypes.c_size_t)]),
+    "sctc_nbest_mbr_batch": (ctypes.c_int, [ctypes.POINTER(MbrConfig), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                            ctypes.c_size_t, vp]),
     "sctc_ctc_tnc_probs": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp]),
     "sctc_ctc_tnc_empty": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]),
     "sctc_ctc_tnc_grad": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, vp, vp, vp]),

@@ -1345,3 +1345,206 @@ def nbest_oracle(refs, nbest_hyps):
             first_dist[b] = d[0]
         o += count[b]
     return best_index, best_dist, first_dist
+
+
+# ---- word interning, minimum Bayes risk selection and word confidences over n-best lists ----
+
+def _alphabet_space(A, space, what, need_space=True):
+    A = int(A)
+    if not 1 <= A <= 256:
+        raise ValueError("%s: alphabet of %d symbols outside 1..256" % (what, A))
+    if need_space:
+        if space is None or not 1 <= int(space) < A:
+            raise ValueError("%s: the space symbol must lie in [1, %d)" % (what, A))
+    return A, 1 if space is None else int(space)
+
+
+def _intern_launch(labels_dev, U_b, loff, goff, A, space, what):
+    """sctc_intern_words_batch on device labels: (word ids int32 [slots] with -1 in the slots that hold no word,
+    counts int32 [N], status int32 [N]), device tensors"""
+    torch = _sctc.require_gpu()
+    N = int(U_b.shape[0])
+    goff = np.ascontiguousarray(goff, dtype=np.int32)
+    cfg = _sctc.InternConfig(N, int(goff.shape[0]) - 1, A, space, _sctc.i32(U_b), _sctc.i64(loff), _sctc.i32(goff))
+    L = _sctc.lib()
+    nbytes = ctypes.c_size_t(0)
+    _sctc.check(L.sctc_intern_words_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)), what)
+    device = labels_dev.device
+    slots = _sctc.intern_slots(U_b)[1]
+    ids = torch.full((max(1, slots),), -1, dtype=torch.int32, device=device)
+    counts = torch.empty(max(1, N), dtype=torch.int32, device=device)[:N]
+    status = torch.empty(max(1, N), dtype=torch.int32, device=device)[:N]
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=device)
+    rc = L.sctc_intern_words_batch(ctypes.byref(cfg), labels_dev.data_ptr(), ids.data_ptr(), counts.data_ptr(),
+                                   status.data_ptr(), ws.data_ptr(), nbytes.value, _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    return ids, counts, status
+
+
+def _group_offsets(groups, N, what):
+    goff = np.asarray(groups, dtype=np.int64).reshape(-1)
+    if goff.shape[0] < 1 or goff[0] != 0 or goff[-1] != N or (np.diff(goff) < 0).any():
+        raise ValueError("%s: groups must be row offsets that run from 0 to %d and never decrease" % (what, N))
+    return goff.astype(np.int32)
+
+
+def intern_words(seqs, groups, space, A=256, device=False):
+    """Word ids of label rows without a lexicon: a word is a maximal run of symbols other than
+    ``space`` (``str.split()``), and within a group of rows two words get the same id exactly when they are the same
+    run of symbols -- the id is the number, in (row, position) order within the group, of the word's first
+    occurrence.  Distinct out-of-vocabulary words therefore stay distinct, which the lexicon's ids do not offer.
+
+    ``seqs`` as for :func:`lm_score_batch`: a list of CTC symbol-id rows (at most 4095 symbols), or a device triple
+    (ids int32 tensor, U, offsets) read in place.  ``groups``: the G + 1 row offsets of G groups of consecutive rows,
+    from 0 to the number of rows.  Returns (ids, counts): a list of int32 arrays, one per row, and int32 [N]; a row
+    with a symbol outside [1, A) is a ValueError.  ``device=True``: nothing is read back; ids is one flat int32
+    tensor in which row n starts at slot ``sum((U[:n] + 1) // 2)`` (slots past a row's words hold -1), counts a
+    device tensor, and a row with a symbol outside [1, A) has count 0."""
+    what = "intern_words"
+    A, space = _alphabet_space(A, space, what)
+    labels, U_b, loff = _score_seqs(seqs, what, _sctc.MBR_MAX_U)
+    goff = _group_offsets(groups, U_b.shape[0], what)
+    ids, counts, status = _intern_launch(labels, U_b, loff, goff, A, space, what)
+    if device:
+        return ids, counts
+    flat, counts, status = ids.cpu().numpy(), counts.cpu().numpy(), status.cpu().numpy()
+    if (status != 0).any():
+        raise ValueError("%s: row %d has a symbol outside [1, %d)" % (what, int(np.nonzero(status)[0][0]), A))
+    first = _sctc.intern_slots(U_b)[0]
+    return [flat[first[n]:first[n] + counts[n]].copy() for n in range(U_b.shape[0])], counts
+
+
+def word_errors_batch(refs, hyps, space, A=256):
+    """int32 [P, 5]: the columns of :func:`edit_distance_batch` (distance, UP, LEFT, SUB, MATCH with a = ref,
+    b = hyp) counted in WORDS, for P pairs of CTC symbol rows -- what ``editDistance.edit_distance(ref.split(),
+    hyp.split())`` returns.  Every {reference, hypothesis} pair is interned as a group on the device
+    (:func:`intern_words`), the counts come back in one small read-back, and :func:`edit_distance_device` runs on
+    the ids in place."""
+    what = "word_errors_batch"
+    A, space = _alphabet_space(A, space, what)
+    refs, hyps = list(refs), list(hyps)
+    P = len(refs)
+    if len(hyps) != P:
+        raise ValueError("%s: %d references for %d hypotheses" % (what, P, len(hyps)))
+    if P == 0:
+        return np.zeros((0, 5), dtype=np.int32)
+    rows = [r for pair in zip(refs, hyps) for r in pair]
+    labels, U_b, loff = _score_seqs(rows, what, _sctc.MBR_MAX_U)
+    torch = _sctc.require_gpu()
+    ids, counts, status = _intern_launch(labels, U_b, loff, 2 * np.arange(P + 1), A, space, what)
+    back = torch.stack([counts, status]).cpu().numpy()
+    if (back[1] != 0).any():
+        raise ValueError("%s: row %d has a symbol outside [1, %d)" % (what, int(np.nonzero(back[1])[0][0]), A))
+    first = _sctc.intern_slots(U_b)[0]
+    stats = edit_distance_device(ids, back[0][0::2], first[0::2], ids, back[0][1::2], first[1::2])
+    return stats.cpu().numpy()
+
+
+def mbr_nbest(hyps, scores, unit="word", scale=1.0, space=None, order=None, K_b=None, confidences=False,
+              distances=False, device=False, A=256, lengths=None):
+    """Minimum Bayes risk selection over n-best lists on the device: with posteriors
+    ``p_k = w_k / Z``, ``w_k = exp(scale * (s_k - s_max))`` over the real hypotheses of an utterance, the chosen
+    hypothesis is the one of least expected edit distance ``risk_k = sum_j p_j D(k, j)`` to the others, D counted
+    in symbols (``unit="char"``) or in words (``unit="word"``, the words interned per utterance as
+    :func:`intern_words` does; ``space`` is then required).
+
+    hyps: the list of lists that ``decode_beam_batch(..., nbest=K)`` returns, or the device tensors
+    ``(ids, lens, scores)`` of ``decode_beam_batch(..., device=True)`` used in place, with ``lengths`` the frames
+    T_b of the utterances (they fix where the ranks lie in ``ids``).  scores: [B, K], array or device tensor --
+    ``rescored`` of :func:`rescore_nbest` or the first pass's; a hypothesis whose score is not finite, or whose rank
+    is not below ``K_b[b]``, is not real.  order: the ``order`` of :func:`rescore_nbest` ([B, K]) or None; risk
+    ties go to the hypothesis that comes first in it, without it to the lower rank.
+
+    Returns a dict: ``best`` int32 [B] (-1 without a real hypothesis), ``posterior`` and ``risk`` float64 [B, K]
+    (0 and +inf for a rank that is not real), ``order`` int32 [B, K] (ranks by ascending risk, the ranks that are
+    not real last); with ``distances`` also ``dist`` int32 [B, K, K] (-1 for a rank that is not real); with
+    ``confidences`` also ``confidence``, a list of float64 arrays: for every unit of the chosen hypothesis the
+    posterior mass of the hypotheses whose alignment with it (the path of :func:`edit_distance_batch`) has a MATCH
+    there.  ``device=True``: nothing is read back, the values are device tensors and ``confidence`` is the pair
+    (flat float64 tensor, in which utterance b starts at the sum of the earlier utterances' longest unit bounds --
+    U in character unit, ceil(U / 2) in word unit, over the ranks below K_b -- and ``conf_len`` int32 [B])."""
+    what = "mbr_nbest"
+    if unit not in ("char", "word"):
+        raise ValueError("%s: unit must be 'char' or 'word'" % what)
+    words = unit == "word"
+    A, space = _alphabet_space(A, space, what, need_space=words)
+    scale = float(scale)
+    if not np.isfinite(scale) or scale < 0:
+        raise ValueError("%s: scale must be a finite number >= 0" % what)
+    torch = _sctc.require_gpu()
+    if isinstance(hyps, tuple) and len(hyps) == 3 and isinstance(hyps[0], torch.Tensor):
+        if lengths is None:
+            raise ValueError("%s: the device tensors of a search need lengths" % what)
+        ids, lens, _ = hyps
+        Tb = np.ascontiguousarray([int(t) for t in lengths], dtype=np.int64)
+        B = Tb.shape[0]
+        if lens.numel() % max(B, 1):
+            raise ValueError("%s: %d lengths for %d utterances" % (what, lens.numel(), B))
+        K = lens.numel() // max(B, 1)
+        foff = np.concatenate([[0], np.cumsum(Tb)[:-1]]).astype(np.int64) if B else np.zeros(0, np.int64)
+        loff = (K * foff[:, None] + np.arange(K, dtype=np.int64)[None, :] * Tb[:, None]).reshape(-1)
+        labels, U_b, loff = _score_seqs((ids, lens, loff), what, _sctc.MBR_MAX_U)
+    else:
+        B = len(hyps)
+        K = len(hyps[0]) if B else 1
+        if any(len(row) != K for row in hyps):
+            raise ValueError("%s: every utterance must have the same number of hypotheses" % what)
+        labels, U_b, loff = _score_seqs([h for row in hyps for h in row], what, _sctc.MBR_MAX_U)
+    if not 1 <= K <= _sctc.NBEST_MAX_K:
+        raise ValueError("%s: %d hypotheses per utterance outside 1..%d" % (what, K, _sctc.NBEST_MAX_K))
+    device_ = labels.device
+    if isinstance(scores, torch.Tensor):
+        sc = scores.to(device=device_, dtype=torch.float64).reshape(-1).contiguous()
+    else:
+        sc = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)).to(device_)
+    if sc.numel() != B * K:
+        raise ValueError("%s: scores must be [B, K]" % what)
+    od = None
+    if order is not None:
+        if isinstance(order, torch.Tensor):
+            od = order.to(device=device_, dtype=torch.int32).reshape(-1).contiguous()
+        else:
+            od = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32).reshape(-1)).to(device_)
+        if od.numel() != B * K:
+            raise ValueError("%s: order must be [B, K]" % what)
+    Kb = np.full(B, K, dtype=np.int32) if K_b is None else np.ascontiguousarray(K_b, dtype=np.int32).reshape(-1)
+    if Kb.shape[0] != B or (B and (Kb.min() < 0 or Kb.max() > K)):
+        raise ValueError("%s: K_b must be [B] with entries in 0..%d" % (what, K))
+    loff = np.ascontiguousarray(loff, dtype=np.int64)
+    flags = (_sctc.MBR_CONF if confidences else 0) | (_sctc.MBR_DIST if distances else 0)
+    cfg = _sctc.MbrConfig(B, K, _sctc.MBR_WORDS if words else _sctc.MBR_CHARS, flags, A, space, scale, _sctc.i32(Kb),
+                          _sctc.i32(U_b), _sctc.i64(loff))
+    L = _sctc.lib()
+    nbytes = ctypes.c_size_t(0)
+    _sctc.check(L.sctc_nbest_mbr_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)), what)
+    post = torch.empty((B, K), dtype=torch.float64, device=device_)
+    risk = torch.empty((B, K), dtype=torch.float64, device=device_)
+    best = torch.empty(B, dtype=torch.int32, device=device_)
+    m_order = torch.empty((B, K), dtype=torch.int32, device=device_)
+    dist = torch.empty((B, K, K), dtype=torch.int32, device=device_) if distances else None
+    conf = conf_len = None
+    if confidences:
+        bound = ((U_b.astype(np.int64) + 1) // 2 if words else U_b.astype(np.int64)).reshape(B, K)
+        bound = np.where(np.arange(K)[None, :] < Kb[:, None], bound, 0)
+        conf_first = np.concatenate([[0], np.cumsum(bound.max(axis=1) if B else [])]).astype(np.int64)
+        conf = torch.zeros(max(1, int(conf_first[-1])), dtype=torch.float64, device=device_)
+        conf_len = torch.zeros(max(1, B), dtype=torch.int32, device=device_)[:B]
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=device_)
+    rc = L.sctc_nbest_mbr_batch(ctypes.byref(cfg), labels.data_ptr(), sc.data_ptr(), od.data_ptr() if od is not None else None,
+                                post.data_ptr(), risk.data_ptr(), best.data_ptr(), m_order.data_ptr(),
+                                dist.data_ptr() if distances else None, conf.data_ptr() if confidences else None,
+                                conf_len.data_ptr() if confidences else None, ws.data_ptr(), nbytes.value,
+                                _sctc.current_stream_ptr())
+    _sctc.check(rc, what)
+    out = {"best": best, "posterior": post, "risk": risk, "order": m_order}
+    if distances:
+        out["dist"] = dist
+    if device:
+        if confidences:
+            out["confidence"] = (conf, conf_len)
+        return out
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    if confidences:
+        flat, n = conf.cpu().numpy(), conf_len.cpu().numpy()
+        out["confidence"] = [flat[conf_first[b]:conf_first[b] + n[b]].copy() for b in range(B)]
+    return out

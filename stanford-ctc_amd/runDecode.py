@@ -286,8 +286,33 @@ def main(argv=None):
     ap.add_argument("--rescore-word-alpha", type=float, default=1.0,
                     help="weight of the word LM's natural-log score in the second pass (default 1)")
     ap.add_argument("--rescore-word-beta", type=float, default=0.0, help="bonus per word of the second pass (default 0)")
+    ap.add_argument("--wer", action="store_true",
+                    help="also print the word error rate of the character method: the words interned on the device "
+                         "(ctc_fast.word_errors_batch), so that distinct out-of-vocabulary words stay distinct")
+    ap.add_argument("--mbr", choices=("char", "word"),
+                    help="write the minimum Bayes risk hypothesis of the n-best list instead of the top-ranked one: least "
+                         "expected edit distance in symbols or in words under the list's posteriors (ctc_fast.mbr_nbest); "
+                         "the list is that of --rescore-nbest K with its second-pass scores, or the first pass's --mbr-nbest K")
+    ap.add_argument("--mbr-scale", type=float, default=None, help="posterior scale of --mbr (default 1): w = exp(S * (s - s_max))")
+    ap.add_argument("--mbr-nbest", type=int, default=0, metavar="K", help="hypotheses of the first pass under --mbr, K <= beam")
+    ap.add_argument("--ctm-conf", action="store_true",
+                    help="with --ctm and --mbr word: a sixth CTM column, the posterior mass of the hypotheses that agree with the word")
     a = ap.parse_args(argv)
     K = a.nbest_oracle
+    if (a.mbr or a.mbr_nbest or a.mbr_scale is not None or a.ctm_conf) and a.method == "bg":
+        ap.error("--mbr, --mbr-scale, --mbr-nbest and --ctm-conf are for the character method")
+    if not a.mbr and (a.mbr_nbest or a.mbr_scale is not None):
+        ap.error("--mbr-nbest and --mbr-scale need --mbr {char,word}")
+    if a.mbr and bool(a.mbr_nbest) == bool(a.rescore_nbest):
+        ap.error("--mbr needs the list of --rescore-nbest K or of --mbr-nbest K, one of the two")
+    if a.mbr_nbest and not 1 <= a.mbr_nbest <= a.beam:
+        ap.error("--mbr-nbest K needs 1 <= K <= beam")
+    if a.mbr_scale is not None and not (np.isfinite(a.mbr_scale) and a.mbr_scale >= 0):
+        ap.error("--mbr-scale must be a finite number >= 0")
+    if a.ctm_conf and not (a.ctm and a.mbr == "word"):
+        ap.error("--ctm-conf needs --ctm FILE and --mbr word")
+    if a.wer and a.method == "bg":
+        ap.error("--wer is for the character method (--method bg reports its WER already)")
     if K and a.method == "bg":
         ap.error("--nbest-oracle is for the character method")
     if a.ctm and a.method == "bg":
@@ -321,7 +346,15 @@ def main(argv=None):
                                           order=a.rescore_word_lm_order)
     keys = sorted(ll)
     errs = n_ref = oracle_errs = n_changed = 0
+    w_errs = w_ref = 0
     space_id = dec.char_int_map.get(a.space)
+    if (a.wer or a.mbr == "word") and space_id is None:
+        ap.error("--wer and --mbr word need the word separator %s in --chars" % a.space)
+    Km = Kr or a.mbr_nbest
+    n_mbr_changed = 0
+    n_sym = max(dec.char_int_map.values()) + 2      # --wer, --mbr: a token the map does not know is a symbol of its own
+    if (a.wer or a.mbr) and n_sym > 256:
+        ap.error("--wer and --mbr take character maps of at most 254 symbols, --chars has ids up to %d" % (n_sym - 2))
     with open(a.out, "w") as out, ErrorLog(a.errors) as log, RefScoreLog(a.ref_scores) as ref_log, \
             open(a.ctm or os.devnull, "w") as ctm:
         for g in range(0, len(keys), a.batch):
@@ -334,9 +367,20 @@ def main(argv=None):
                                        rescore_word_beta=a.rescore_word_beta)
                 n_changed += sum(dec.rescore_changed)
             else:
-                res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, 1))
-            if max(K, Kr) <= 1:
+                res = dec.decode_batch(probs, a.beam, a.alpha, a.beta, nbest=max(K, a.mbr_nbest, 1))
+            if max(K, Kr, a.mbr_nbest) <= 1:
                 res = [[r] for r in res]
+            conf = None
+            if a.mbr:           # the first Km ranks of every list, in the order the pass left them: ties go to the earlier
+                cand_ids = [[[dec.char_int_map.get(t, n_sym - 1) for t in tokens(h, dec.char_int_map)] for h, _ in row[:Km]]
+                            for row in res]
+                m = ctc_fast.mbr_nbest(cand_ids, [[s for _, s in row[:Km]] for row in res], unit=a.mbr,
+                                       scale=1.0 if a.mbr_scale is None else a.mbr_scale, space=space_id, A=n_sym,
+                                       confidences=a.ctm_conf)
+                conf = m.get("confidence")
+                pick = [max(int(b), 0) for b in m["best"]]
+                n_mbr_changed += sum(b != 0 for b in pick)
+                res = [[row[b]] + row[:b] + row[b + 1:] for row, b in zip(res, pick)]
             if ref_log.f:       # the transcripts of the batch under the search's objective, one call
                 idx = [i for i, k in enumerate(ks) if k in alis]
                 ref_ids = [[dec.char_int_map.get(t, -1) for t in alis[ks[i]]] for i in idx]
@@ -348,8 +392,11 @@ def main(argv=None):
             if a.ctm:           # every 1-best hypothesis aligned to its own utterance, one call
                 hyp_ids = [[dec.char_int_map[t] for t in tokens(row[0][0], dec.char_int_map)] for row in res]
                 _, spans, _, _, _ = ctc_fast.align_batch(probs, hyp_ids)
-                for k, ids, sp in zip(ks, hyp_ids, spans):
-                    ctm.writelines(ctm_lines(k, ctm_words(ids, sp, space_id, dec.int_char_map), a.frame_shift))
+                for i, (k, ids, sp) in enumerate(zip(ks, hyp_ids, spans)):
+                    lines = ctm_lines(k, ctm_words(ids, sp, space_id, dec.int_char_map), a.frame_shift)
+                    if a.ctm_conf:      # an utterance without an alignment has no lines
+                        lines = ["%s %.4f\n" % (l[:-1], c) for l, c in zip(lines, conf[i])]
+                    ctm.writelines(lines)
             scored, refs, cand, lists = [], [], [], []
             for k, row in zip(ks, res):
                 out.write("%s %.6f %s\n" % (k, row[0][1], row[0][0]))
@@ -364,6 +411,11 @@ def main(argv=None):
                 errs += int(st[0])
                 n_ref += len(ref)
                 log.add(k, st)
+            if a.wer and refs:
+                rows = [[dec.char_int_map.get(t, n_sym - 1) for t in r] for r in refs + cand]
+                st = ctc_fast.word_errors_batch(rows[:len(refs)], rows[len(refs):], space_id, A=n_sym)
+                w_errs += int(st[:, 0].sum())
+                w_ref += int((st[:, 1] + st[:, 3] + st[:, 4]).sum())      # a = ref: every word of it is UP, SUB or MATCH
             if K:
                 table = {}
                 ids = [[table.setdefault(t, len(table)) for t in r] for r in refs]
@@ -371,10 +423,14 @@ def main(argv=None):
                 oracle_errs += int(ctc_fast.nbest_oracle(ids, nb)[1].sum()) if ids else 0
     cer = errs / float(max(n_ref, 1))
     print("decoded %d utterances, CER %.4f (%d / %d)" % (len(keys), cer, errs, n_ref))
+    if a.wer:
+        print("WER %.4f (%d / %d words)" % (w_errs / float(max(w_ref, 1)), w_errs, w_ref))
     log.summary()
     ref_log.summary()
     if Kr:
         print("rescored: %d of %d utterances changed their 1-best" % (n_changed, len(keys)))
+    if a.mbr:
+        print("mbr (%s): %d of %d utterances changed their 1-best" % (a.mbr, n_mbr_changed, len(keys)))
     if K:
         print("oracle CER of %d-best %.4f (%d / %d), 1-best CER %.4f (%d / %d)"
               % (K, oracle_errs / float(max(n_ref, 1)), oracle_errs, n_ref, cer, errs, n_ref))
