@@ -498,7 +498,11 @@ __global__ __launch_bounds__(64 * W) void ctc_fusedw_kernel(CtcFusedArgs<RI> p, 
     {
         const int got = meet(0, 1 + skip);
         timed_out |= got == 0;
-        if (got != 1) skip |= 2;      // the partner failed in phase 0 (or never came): nothing to multiply with
+        // the partner failed in phase 0 (or never came): nothing to multiply with.  Alpha goes on all the same when beta has
+        // failed: the zero band sum lies behind the middle, and the cost is -llForward as far as ALPHA gets
+        // (ctc_fast.pyx:147-149) -- it meets the same zero in its phase 1; what it multiplies and writes on the way is
+        // taken back below like every row of an utterance that skips
+        if (got == 0 || (got != 1 && dir == 1)) skip |= 2;
     }
     load_lists();
     if (Tst == 0 && !skip) {

@@ -154,10 +154,14 @@ int launch_argmax_rows(const void* y, int dtype, int32_t* best, int64_t rows, in
 // the gradient -- are reproduced exactly.  LAZY (SCTC_CTC_LAZY=1, float32 probabilities only)
 // rescales every 4th frame instead: the per-frame scale cancels in the gradient (:138-145),
 // float32's smallest value 1e-45 keeps four unscaled float64 steps above 1e-180, llForward is
-// the log of the last frame's mass minus the logs of the applied factors -- the same number --
+// the log of the last frame's mass minus the logs of the applied factors -- the same number
+// (measured: 1.4e-15 relative against the reference's sum, tests/test_gpu_ctc_lazy.py) --
 // and the 64-lane reduction + division leave most steps of the dependency chain (0.44 instead
-// of 0.7 ms at cfg-3).  It is numerically MORE robust than the reference (no underflow of the
-// forward-backward overlap), which is exactly why it is not the default: parity first.
+// of 0.7 ms at cfg-3).  It is not the reference's operation order, which is why it is not the
+// default: parity first.  It is NOT more robust than the reference where the forward-backward
+// overlap underflows: ctc_grad_kernel brings the two ROWS to unit magnitude, the states that
+// carry their overlap stay hundreds of binary orders below (measured at T = 8000 / U = 800: as
+// far from an exact model as the default schedule).
 template <typename RI, int K, int NA, int W, bool LAZY>
 __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> p)
 {
@@ -451,12 +455,38 @@ __global__ __launch_bounds__(64 * W) void ctc_lattice_kernel(CtcLatticeArgs<RI> 
     // stored them reads them back (its own stores, drained first; the lines were never cached):
     // lane l takes frames l, l+64, ... in ascending order -- the order the in-register scheme this
     // replaces summed them in, so llForward is bit-identical to it.
+    // Lazy schedule, a band that ran dry: the zero is noticed at the next rescaled frame (first_bad), up to RS - 1 frames
+    // behind the dry one, and the rows in between were stored unscaled, with the factor 1.  The reference's cost is
+    // -llForward as far as alpha got (ctc_fast.pyx:147-149), which includes the band sums of those rows: their product is
+    // the mass of the last row before the dry one.  That row's states were stored by every wave: the block meets first
+    // (first_bad is the same in every wave -- it comes from the band sum they share).
+    if constexpr (LAZY) {
+        if (first_bad != NO_BAD) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
+    }
     if (wave == W - 1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         double ll = 0.0;   // per-lane partial of llForward (float64 like the reference)
         const R* fac = lat + (LP - 1);
         for (int tau = lane; tau < n_rows; tau += 64) ll += log((double)fac[(int64_t)tau * LP]);
         double total = wave_sum(ll);
+        if constexpr (LAZY) {
+            if (first_bad != NO_BAD) {
+                R mass = (R)1;      // of the last row behind the last rescaled frame that is not all zero
+                bool dry = false;
+                for (int tau = (first_bad - 1) / RS * RS + 1; tau < first_bad; ++tau) {
+                    R part = (R)0;
+                    for (int s = lane; s < L; s += 64) part += lat[(int64_t)tau * LP + s];
+                    const R sum = wave_sum(part);
+                    dry = dry || sum == (R)0;
+                    if (!dry) mass = sum;
+                }
+                total += log((double)mass);
+            }
+        }
         if (lane == 0) {
             if (empty_band && !skip) total = -INFINITY;  // math.log(0.0)
             p.ll[2 * b + dir] = total;                   // llForward (dir 0) / llBackward (dir 1)

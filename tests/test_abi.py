@@ -121,6 +121,34 @@ def test_argument_errors_need_no_gpu(sctc):
         del os.environ["SCTC_CTC_WIDE_MIN_B"]
 
 
+@pytest.mark.parametrize("env", [{}, {"SCTC_CTC_WIDE": "1"}, {"SCTC_CTC_FUSED": "0"}, {"SCTC_CTC_GENERIC": "1"}])
+def test_ctc_short_workspace_is_refused_before_anything_is_touched(sctc, env):
+    """sctc_ctc_loss_batch with a workspace 256 bytes (and one byte) shorter than sctc_ctc_workspace_bytes asks for:
+    SCTC_ERR_WORKSPACE on every path, decided on the host -- the pointers here lead nowhere, so touching one of them
+    would end the process (tests/test_gpu_ctc_entry.py checks on real buffers that no byte changes)"""
+    L = sctc.lib()
+    T = np.array([30, 1, 7], dtype=np.int32)
+    U = np.array([12, 1, 9], dtype=np.int32)
+    off = np.array([0, 30, 31], dtype=np.int64)
+    lab = np.ones(22, dtype=np.int32)
+    loff = np.array([0, 12, 13], dtype=np.int64)
+    bt = sctc.CtcBatch(3, 33, 0, sctc.F32, 40, sctc.i32(T), sctc.i32(U), sctc.i64(off), sctc.i32(lab), sctc.i64(loff), None)
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        n = L.sctc_ctc_workspace_bytes(ctypes.byref(bt))
+        assert n > 256 and n % 256 == 0
+        fake = [ctypes.c_void_p(4096 * (i + 1)) for i in range(5)]
+        for short in (256, 1):
+            assert L.sctc_ctc_loss_batch(ctypes.byref(bt), fake[0], fake[1], fake[2], fake[3], fake[4], n - short, None) == -3
+            assert b"workspace" in L.sctc_last_error()
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
 def test_reference_surface_names(sctc):
     import ctc_fast
     from nnets import brnnet

@@ -18,7 +18,9 @@ The header is pure host code: tests/ctc_plan_dump.cpp prints its decisions, comp
   * every name of tests/test_gpu_ctc_paths.py's `path.ENV` reaches the kernel it names on every shape of its SHAPES,
     and the two through-the-network minibatches take the wide kernel by default and the lattice pair with
     SCTC_CTC_FUSED=0 -- what the GPU tests can only infer from numeric differences;
-  * moving any one threshold in a copy of the header makes the table test fail.
+  * moving any one threshold in a copy of the header makes the table test fail;
+  * SCTC_CTC_LAZY=1 selects the lattice kernel's lazy instantiation for float32 batches only, and the cases of
+    tests/test_gpu_ctc_lazy.py and tests/test_gpu_ctc_entry.py reach the instantiations they claim to.
 """
 import os
 import subprocess
@@ -163,6 +165,13 @@ def test_every_named_path_reaches_the_kernel_it_names(dump, name):
             assert _is_lattice_pair(got, ri), tag
             if name != "lattice":        # the forced shapes: that many waves per direction
                 assert _args(got[0])[3] == name[len("lattice"):], tag
+        elif name.startswith("lazy"):
+            # float32: the lattice kernel's lazy instantiation; float64 has none and keeps the reference's schedule -- on the
+            # lattice pair as well: the switch turns the fused kernels off for either dtype
+            assert len(got) == 2 and got[0].startswith("ctc_lattice_kernel<%s, " % ri), tag
+            assert got[1].startswith("ctc_grad_kernel<%s, " % ri) and _args(got[0])[4] == ("false" if dtype else "true"), tag
+            if name != "lazy":
+                assert _args(got[0])[3] == name[len("lazy"):], tag
         else:
             assert name == "generic"
             assert got == ["ctc_lattice_generic_kernel<%s>" % ri, "ctc_grad_generic_kernel<%s>" % ri], tag
@@ -226,6 +235,83 @@ def test_the_bit_pinned_cases_reach_every_instantiation(dump):
             assert values(seen) == values(want), (family, i, values(want) - values(seen))
     # the lattice, gradient and generic kernels: every instantiation
     assert not [n for n in want - seen if not n.startswith("ctc_fused")], sorted(want - seen)
+
+
+def test_the_lazy_switch_selects_the_lazy_lattice_kernel_for_float32_only(dump):
+    """SCTC_CTC_LAZY=1 ("switches"): float32 batches of up to 2048 states and 256 symbols get
+    ctc_lattice_kernel<float, K, NA, W, true> with the K and W of ctc_lattice_shape and the fused kernels are off, whatever
+    the batch size; float64 batches get no lazy kernel (the reference's schedule, on the lattice pair); beyond 2048 states
+    or 256 symbols the generic kernels run and the switch does nothing"""
+    env = paths.path.ENV["lazy"]
+    queries = [(B, A, dtype, L, 50) for B in (1, 17, 24, 300, 1100) for A in (33, 65, 129, 256) for dtype in (0, 1)
+               for L in (3, 128, 129, 256, 257, 512, 513, 1024, 1025, 2047)]
+    for (B, A, dtype, L, T), got in zip(queries, kernels(dump, env, queries)):
+        W = 1 if L <= 256 else (4 if L <= 1024 else 8)
+        K = next(k for k in (2, 4, 8) if L <= 64 * W * k)
+        ri = "double" if dtype else "float"
+        assert got[0] == "ctc_lattice_kernel<%s, %d, %d, %d, %s>" % (ri, K, _na(A), W, "false" if dtype else "true"), (B, A, L, got)
+        assert len(got) == 2 and got[1].startswith("ctc_grad_kernel<%s, " % ri)
+    beyond = [(1, 33, 0, 2049, 50), (1, 257, 0, 65, 50)]
+    assert kernels(dump, env, beyond) == kernels(dump, {}, beyond) == [["ctc_lattice_generic_kernel<float>",
+                                                                       "ctc_grad_generic_kernel<float>"]] * 2
+
+
+def _lazy_missing(dump, shapes):
+    """what of the lazy lattice kernel's template parameters (path name, (A, T, U)) cases do NOT reach: (K, W) pairs of
+    ctc_lattice_shape and values of NA"""
+    seen = set()
+    for which in sorted(set(w for w, _ in shapes)):
+        queries = [(1, A, 0, 2 * U + 1, T) for w, (A, T, U) in shapes if w == which]
+        for got in kernels(dump, paths.path.ENV[which], queries):
+            assert got[0].startswith("ctc_lattice_kernel<float, ") and _args(got[0])[4] == "true", (which, got)
+            seen.add(tuple(int(v) for v in _args(got[0])[1:4]))
+    want_kw = {(2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (2, 4), (4, 4), (8, 4), (2, 8), (4, 8)}
+    return (want_kw - {(k, w) for k, _, w in seen}) | ({("NA", n) for n in (1, 2, 4)} - {("NA", n) for _, n, _ in seen})
+
+
+def test_the_lazy_gpu_cases_reach_every_lazy_instantiation(dump):
+    """tests/test_gpu_ctc_lazy.LAZY_SHAPES (its cases against the oracle) run the lazy schedule in every (K, W) of
+    ctc_lattice_shape and with 1, 2 and 4 probability registers per frame; a list without its forced shapes, or without its
+    wide alphabets, does not"""
+    from tests import test_gpu_ctc_lazy as lazy
+    assert _lazy_missing(dump, lazy.LAZY_SHAPES) == set()
+    assert _lazy_missing(dump, [c for c in lazy.LAZY_SHAPES if c[0] != "lazy8"]) == {(2, 8)}
+    assert _lazy_missing(dump, [c for c in lazy.LAZY_SHAPES if c[0] != "lazy1"]) == {(8, 1), (16, 1), (32, 1)}
+    assert ("NA", 4) in _lazy_missing(dump, [c for c in lazy.LAZY_SHAPES if c[1][0] <= 128])
+
+
+def _entry_missing(dump, cases):
+    """kernel families, and values of NA per family that has the parameter, that (id, path, row, A, blank, dtype) cases
+    of tests/test_gpu_ctc_entry.py do not reach with their seven-utterance batch"""
+    seen = set()
+    for _, which, row, A, _, dt in cases:
+        U, T = paths._ROWS[row]
+        seen.update(kernels(dump, paths.path.ENV[which], [(7, A, int(dt == np.float64), 2 * U + 1, T)])[0])
+    missing = set()
+    for family, na_at in (("ctc_fused_kernel", 3), ("ctc_fusedw_kernel", 3), ("ctc_lattice_kernel", 2), ("ctc_grad_kernel", None),
+                          ("ctc_lattice_generic_kernel", None), ("ctc_grad_generic_kernel", None)):
+        mine = [n for n in seen if n.startswith(family + "<")]
+        if not mine:
+            missing.add(family)
+        elif na_at is not None:
+            missing |= {(family, "NA", n) for n in (1, 2, 4)} - {(family, "NA", int(_args(n)[na_at])) for n in mine}
+    if not any(n.startswith("ctc_lattice_kernel<float, ") and _args(n)[4] == "true" for n in seen):
+        missing.add("the lazy schedule")
+    if not any(n.startswith("ctc_fused_kernel<") and _args(n)[5] == "true" for n in seen):
+        missing.add("the dieted fused kernel")
+    return missing
+
+
+def test_the_entry_cases_reach_every_kernel_family_and_register_count(dump):
+    """tests/test_gpu_ctc_entry.CASES: every kernel family (fused with and without helper waves and dieted, wide, lattice
+    in both schedules, gradient, the generic pair) and, of the three families with the parameter, NA = 1, 2 and 4; taking
+    a path's rows away is noticed"""
+    from tests import test_gpu_ctc_entry as entry
+    assert _entry_missing(dump, entry.CASES) == set()
+    assert _entry_missing(dump, [c for c in entry.CASES if not c[1].startswith("wide")]) >= {"ctc_fusedw_kernel"}
+    assert _entry_missing(dump, [c for c in entry.CASES if c[1] != "generic"]) == {"ctc_lattice_generic_kernel",
+                                                                                    "ctc_grad_generic_kernel"}
+    assert ("ctc_fused_kernel", "NA", 4) in _entry_missing(dump, [c for c in entry.CASES if c[3] != 200])
 
 
 # (text of csrc/ctc_plan.h, its replacement): each moves one threshold by one or two

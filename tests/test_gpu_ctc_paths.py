@@ -47,9 +47,13 @@ class path:
            # the lattice kernel's forced shapes (ctc_lattice_shape: 8 / 16 / 32 states per lane on one wave, 8 on four
            # waves, 2 on eight)
            "lattice1": {"SCTC_CTC_FUSED": "0", "SCTC_CTC_WAVES": "1"}, "lattice4": {"SCTC_CTC_FUSED": "0", "SCTC_CTC_WAVES": "4"},
-           "lattice8": {"SCTC_CTC_FUSED": "0", "SCTC_CTC_WAVES": "8"}}
+           "lattice8": {"SCTC_CTC_FUSED": "0", "SCTC_CTC_WAVES": "8"},
+           # the lattice kernel's lazy schedule (float32 probabilities rescale every 4th frame; INTEGRATION.md, "switches") and
+           # its forced shapes: tests/test_gpu_ctc_lazy.py, tests/test_gpu_ctc_entry.py
+           "lazy": {"SCTC_CTC_LAZY": "1"}, "lazy1": {"SCTC_CTC_LAZY": "1", "SCTC_CTC_WAVES": "1"},
+           "lazy4": {"SCTC_CTC_LAZY": "1", "SCTC_CTC_WAVES": "4"}, "lazy8": {"SCTC_CTC_LAZY": "1", "SCTC_CTC_WAVES": "8"}}
     VARS = ("SCTC_CTC_STORE", "SCTC_CTC_FUSED", "SCTC_CTC_GENERIC", "SCTC_CTC_HELPER", "SCTC_CTC_DIET_MIN_B", "SCTC_CTC_WIDE",
-            "SCTC_CTC_WAVES", "SCTC_CTC_WIDE_MIN_B")
+            "SCTC_CTC_WAVES", "SCTC_CTC_WIDE_MIN_B", "SCTC_CTC_LAZY")
 
     def __init__(self, name):
         self.env = self.ENV[name]
