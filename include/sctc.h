@@ -777,6 +777,72 @@ int sctc_ctc_tnc_empty(const sctc_tnc_config* cfg, const void* probs_dev, const 
 int sctc_ctc_tnc_grad(const sctc_tnc_config* cfg, const void* grad_dev, const int32_t* T_n_dev, const double* cost_dev,
                       const int32_t* skip_dev, const double* scale_dev, void* out_dev, void* stream);
 
+/* ---- minimum word error rate training over n-best lists (ctc_torch.mwer_loss) -----
+ * Added without an ABI version bump (still 6): sctc_ctc_mwer_probs, sctc_ctc_mwer_coef, sctc_ctc_mwer_combine.
+ *
+ * Utterance n of a time-major [T, N, C] tensor has frames T_n and hypotheses k < K_n[n] <= K with label rows y_k
+ * (length U_k >= 0, labels in [0, C), none equal to the blank) and errors W_k (float64, any unit the caller likes).
+ *   ll_k     = log P_ctc(y_k | x_n), float64: minus the cost the CTC kernels return for that label row over that
+ *              utterance's probabilities.
+ *   real     hypothesis k is REAL when k < K_n[n], W_k is finite, the CTC call's skip is 0 and its cost is finite.
+ *            Everything else has weight 0 and is never read beyond that test.
+ *   active   an utterance is ACTIVE when T_n >= 2 and it has at least one real hypothesis.  An inactive utterance has
+ *            loss 0 and gradient rows of exact zeros.  (One frame is the shape where the CTC kernels follow the
+ *            reference to -log(p_blank + p_label) instead of the CTC loss; MWER over one frame is of no use, so it is
+ *            left out, not special-cased.)
+ *   weights  m = max ll_k over the real ones; w_k = exp(scale * (ll_k - m)), exactly 1.0 where ll_k == m;
+ *            Z = sum w_k in ascending k; P_k = w_k / Z; R = sum P_k * W_k in ascending k, the expected error;
+ *            Wbar = (sum W_k, ascending k) / (number of real hypotheses).  All float64, no contraction.
+ *   loss     loss_n = R - Wbar, or R alone with subtract_mean == 0.  The baseline changes the value, never the
+ *            gradient.
+ *   coef     c_k = scale * P_k * (W_k - R) = d loss_n / d ll_k.
+ *   gradient d loss_n / d input[t, n, c] = sum_k c_k * occ_k[t, c] for t < T_n, exact 0 for padded frames, where
+ *            occ_k = p - g_k is the occupancy of symbol c at frame t under hypothesis k, p the probabilities and g_k
+ *            the gradient row the CTC kernels return.  Because sum_k c_k = 0 the p term cancels: the sum is the exact
+ *            derivative both with respect to activations in front of a softmax and with respect to raw
+ *            log-probabilities.
+ *
+ * The scheme: a buffer [T][N * K][C] is a batch of sctc_ctc_loss_batch as it stands, with rowbase[t] = t * N * K,
+ * frame_off = n * K + k and ld = C, and a [T, N * K, C] batch of sctc_ctc_tnc_empty (the hypotheses with U == 0).  The
+ * three entries are what surrounds those calls.  Each returns SCTC_ERR_ARG (no device needed) for a NULL config, T < 0,
+ * N < 0, K outside 1..256, C < 1, an unknown dtype or mode, T * N * K beyond INT32_MAX, a scale that is not finite or
+ * is < 0, a subtract_mean other than 0 and 1, and a NULL pointer with work to do.  T == 0 or N == 0 launches nothing.
+ * No entry allocates device memory; every launch goes to `stream`; no float atomics and no waiting on another
+ * workgroup: each is deterministic bit for bit. */
+typedef struct sctc_mwer_config {
+    int32_t T, N, K, C;           /* frames, utterances (>= 0), hypotheses per utterance (1..256), alphabet (>= 1) */
+    int32_t dtype;                /* SCTC_F32 | SCTC_F64: type of the strided tensor, of probs, the gradient rows and G */
+    int32_t mode;                 /* SCTC_TNC_LOG_PROBS | SCTC_TNC_LOGITS */
+    int64_t stride_t, stride_n, stride_c;   /* element strides of the strided [T, N, C] input of sctc_ctc_mwer_probs */
+    double scale;                 /* finite, >= 0: multiplies the log-likelihood differences */
+    int32_t subtract_mean;        /* 0 | 1 */
+} sctc_mwer_config;
+
+/* The prologue, §4.13's (exp of log-probabilities, or the softmax in the arithmetic of sctc_softmax_rows), computed
+ * once per (t, n) from the strided input_dev and stored to the K_n[n] consecutive rows (t * N + n) * K + k of
+ * probs_dev [T * N * K][C].  T_n_dev, K_n_dev device int32 [N].  Padded frames t >= T_n[n] and ranks >= K_n[n] are
+ * neither read nor written.  A row per lane for C <= 32, a row per wave beyond. */
+int sctc_ctc_mwer_probs(const sctc_mwer_config* cfg, const void* input_dev, const int32_t* T_n_dev, const int32_t* K_n_dev,
+                        void* probs_dev, void* stream);
+
+/* One wave per utterance.  cost_dev double [N * K], skip_dev int32 [N * K]: what the CTC calls returned for pair
+ * n * K + k (any finite or non-finite value where none was made: the caller marks those with skip != 0);
+ * errors_dev double [N * K].  Outputs: loss_dev double [N]; coef_dev double [N * K], exact +0.0 where the rank is not
+ * real or the utterance inactive; posterior_dev double [N * K], 0 there; expected_dev double [N], R (0 when inactive);
+ * real_dev int32 [N * K], 1 for the real ranks of an active utterance; inactive_dev int32 [N]. */
+int sctc_ctc_mwer_coef(const sctc_mwer_config* cfg, const double* cost_dev, const int32_t* skip_dev, const double* errors_dev,
+                       const int32_t* T_n_dev, const int32_t* K_n_dev, double* loss_dev, double* coef_dev,
+                       double* posterior_dev, double* expected_dev, int32_t* real_dev, int32_t* inactive_dev, void* stream);
+
+/* out_dev [T * N][C] (contiguous): row t * N + n is sum over the real k, ascending, of coef_k * (double(p) -
+ * double(g_k)), rounded once to dtype, for t < T_n[n] of the active utterances; the other rows are not written.
+ * probs_dev, grad_dev [T * N * K][C]: the prologue's output and the gradient rows of the CTC calls.  By select: no row
+ * of a rank that is not real is read; p is read from the first real rank's row (every rank's row of a (t, n) holds the same p).
+ * The result is a gradient buffer of sctc_ctc_tnc_grad with skip = inactive and cost = 0. */
+int sctc_ctc_mwer_combine(const sctc_mwer_config* cfg, const void* probs_dev, const void* grad_dev, const double* coef_dev,
+                          const int32_t* real_dev, const int32_t* T_n_dev, const int32_t* inactive_dev, void* out_dev,
+                          void* stream);
+
 /* ---- BRNN: ctc_fast/nnets/brnnet.py NNet ------------------------------- */
 
 typedef struct sctc_brnn_config {

@@ -168,6 +168,14 @@ class TncConfig(ctypes.Structure):
 TNC_LOG_PROBS, TNC_LOGITS = 0, 1
 TNC_LANE_MAX_C = 32         # csrc/ctc_tnc.hip: rows up to this take a row per lane in the prologue, wider ones a row per wave
 
+
+class MwerConfig(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("dtype", ctypes.c_int32), ("mode", ctypes.c_int32), ("stride_t", ctypes.c_int64),
+                ("stride_n", ctypes.c_int64), ("stride_c", ctypes.c_int64), ("scale", ctypes.c_double),
+                ("subtract_mean", ctypes.c_int32)]
+
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -247,6 +255,9 @@ PROTOTYPES = {
     "sctc_ctc_tnc_probs": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp]),
     "sctc_ctc_tnc_empty": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]),
     "sctc_ctc_tnc_grad": (ctypes.c_int, [ctypes.POINTER(TncConfig), vp, vp, vp, vp, vp, vp, vp]),
+    "sctc_ctc_mwer_probs": (ctypes.c_int, [ctypes.POINTER(MwerConfig), vp, vp, vp, vp, vp]),
+    "sctc_ctc_mwer_coef": (ctypes.c_int, [ctypes.POINTER(MwerConfig), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "sctc_ctc_mwer_combine": (ctypes.c_int, [ctypes.POINTER(MwerConfig), vp, vp, vp, vp, vp, vp, vp, vp]),
     "sctc_brnn_query": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), ctypes.POINTER(BrnnSizes)]),
     "sctc_brnn_create": (ctypes.c_int, [ctypes.POINTER(BrnnConfig), vp, vp, vp, ctypes.c_size_t,
                                         ctypes.POINTER(vp)]),
