@@ -982,6 +982,73 @@ int sctc_brnn_forward(sctc_brnn_t h, const sctc_minibatch* mb, float* probs_dev,
 int sctc_brnn_ctc_workspace_bytes(sctc_brnn_t h, const sctc_minibatch* mb, size_t* needed, size_t* reserved);
 int sctc_brnn_set_ctc_workspace(sctc_brnn_t h, void* workspace_dev, size_t workspace_bytes);
 
+/* ---- MWER inside the step: the BRNN trained on expected word error -----
+ * Added without an ABI version bump (still 6): sctc_brnn_mwer_cost_and_grad, sctc_brnn_mwer_cost_and_grad_async,
+ * sctc_brnn_mwer_workspace_bytes, sctc_brnn_set_mwer_workspace.
+ *
+ * One forward pass, the CTC recursions of every hypothesis (and of the reference), one backward pass.  Utterance b
+ * (caller order) of the minibatch has frames T_b and hypotheses k < K_b[b] <= K with label rows y_{b,k} (length U >= 0,
+ * labels in [1, A): the blank, 0, is an argument error) and errors W_{b,k} (float64).  real, active, weights, loss,
+ * coefficients and the gradient with respect to the output layer's activations are those of the MWER block above
+ * (n = b; the baseline is subtract_mean).  Three additions:
+ *   ctc_weight   lambda, finite and >= 0.  With lambda > 0 the reference rows mb->labels / mb->U_b are required (U >= 1,
+ *                as in sctc_brnn_cost_and_grad); the step's loss is loss_b + lambda * ctc_b and the output-layer gradient
+ *                sum_k c_k (p - g_k) + lambda * g_ref.  An utterance whose reference CTC call skips, or whose cost is not
+ *                finite, contributes no lambda term.  The reference row is never part of the posterior.  With lambda == 0
+ *                the reference labels are not read and may be NULL; ctc_cost and ctc_skip then come back 0.
+ *   empty        a hypothesis with U == 0 (all blank) is real: cost -sum_t log p[t, blank] in ascending t, gradient rows
+ *                p - onehot(blank); skip and cost +inf when a p_blank is 0.
+ *   inactive     an utterance with T_b < 2 or without a real hypothesis leaves exact zeros in its rows of the output
+ *                layer's delta; with lambda > 0 and a usable reference row it gets lambda * g_ref.
+ * hyp_U and errors are host [B * K], b-major; hyp_labels is concatenated over the slots the contract reads, in that
+ * order: a slot with k >= K_b[b] or a non-finite error carries no labels, and neither its labels nor its hyp_U are
+ * looked at.  Gradients are summed over utterances like sctc_brnn_cost_and_grad's, under the same SCTC_FLAG_ACCUMULATE
+ * and SCTC_FLAG_NO_REG_GRAD; SCTC_FLAG_SYNC_SKIP is SCTC_ERR_ARG here.  Two runs are bit-equal: no float atomics, no
+ * waiting on another workgroup in the kernels this adds. */
+typedef struct sctc_mwer_minibatch {
+    int32_t K;                  /* hypothesis slots per utterance, 1..256 */
+    const int32_t* K_b;         /* host [B], 0..K */
+    const int32_t* hyp_labels;  /* host, concatenated (may be NULL when no slot that is read has a label) */
+    const int32_t* hyp_U;       /* host [B * K] */
+    const double* errors;       /* host [B * K] */
+    double scale;               /* finite, >= 0 */
+    int32_t subtract_mean;      /* 0 | 1 */
+    double ctc_weight;          /* finite, >= 0 */
+} sctc_mwer_minibatch;
+
+/* every pointer optional (a NULL struct: no outputs); caller order; host pointers for sctc_brnn_mwer_cost_and_grad,
+ * device pointers for the _async entry */
+typedef struct sctc_mwer_outputs {
+    double* loss;       /* [B]  loss_b + lambda * ctc_b */
+    double* expected;   /* [B]  R, the expected error (0 when inactive) */
+    int32_t* inactive;  /* [B] */
+    double* ctc_cost;   /* [B]  the reference row's CTC cost (lambda > 0) */
+    int32_t* ctc_skip;  /* [B]  1 where that call skipped or its cost is not finite: no lambda term */
+    double* posterior;  /* [B * K]  P_k, 0 where not real */
+    int32_t* real;      /* [B * K] */
+} sctc_mwer_outputs;
+
+/* The step's device workspace is owned by the caller (the sctc_brnn_set_ctc_workspace pattern): the two K-fold buffers
+ * [N * S][A] float (S = K, + 1 with lambda > 0), the CTC workspace of the label rows and the small per-slot arrays
+ * (csrc/brnn_mwer_plan.h).  sctc_brnn_mwer_workspace_bytes validates the minibatch and the descriptor exactly as the
+ * step does and says how much THIS minibatch needs; sctc_brnn_set_mwer_workspace hands a 256-byte aligned buffer over
+ * (NULL and 0: none), which the caller keeps alive until it sets another one or destroys the handle.  A step without
+ * enough workspace returns SCTC_ERR_WORKSPACE.  sctc_brnn_query's answer does not include it. */
+int sctc_brnn_mwer_workspace_bytes(sctc_brnn_t h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, size_t* needed);
+int sctc_brnn_set_mwer_workspace(sctc_brnn_t h, void* workspace_dev, size_t workspace_bytes);
+
+/* SCTC_ERR_ARG before any launch: a NULL handle, minibatch, descriptor or descriptor field, K outside 1..256, a K_b
+ * outside 0..K, a negative hyp_U or a label outside [1, A) in a slot that is read, a scale or ctc_weight that is not
+ * finite or is < 0, a subtract_mean other than 0 and 1, N * S beyond INT32_MAX, SCTC_FLAG_SYNC_SKIP, a model created
+ * with train = 0.  The scalars of the descriptor are checked first, without a device or a handle.
+ * The step is re-run after SCTC_ERR_TIMEOUT like sctc_brnn_cost_and_grad's (not when accumulating); its CTC and MWER
+ * kernels are timed under SCTC_PHASE_CTC.  *regcost_host as in sctc_brnn_cost_and_grad. */
+int sctc_brnn_mwer_cost_and_grad(sctc_brnn_t h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, int32_t flags,
+                                 const sctc_mwer_outputs* out_host, double* regcost_host, void* stream);
+/* same, the outputs stay on the device (no host sync); follow up with sctc_brnn_check */
+int sctc_brnn_mwer_cost_and_grad_async(sctc_brnn_t h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, int32_t flags,
+                                       const sctc_mwer_outputs* out_dev, void* stream);
+
 /* rocprof-free timing hooks: milliseconds spent in the phases of the last call, measured with hipEvents
  * on the step's stream.  sctc_brnn_set_profiling(h, 1): exact phase timers that synchronise the
  * stream at every phase change (perturbing); (h, 2): asynchronous -- one event per phase change is

@@ -176,6 +176,19 @@ class MwerConfig(ctypes.Structure):
                 ("subtract_mean", ctypes.c_int32)]
 
 
+class MwerMinibatch(ctypes.Structure):
+    _fields_ = [("K", ctypes.c_int32), ("K_b", c_i32p), ("hyp_labels", c_i32p), ("hyp_U", c_i32p), ("errors", c_f64p),
+                ("scale", ctypes.c_double), ("subtract_mean", ctypes.c_int32), ("ctc_weight", ctypes.c_double)]
+
+
+class MwerOutputs(ctypes.Structure):
+    """every field optional: host pointers for the synchronous entry, device pointers for the _async one"""
+    _fields_ = [("loss", vp), ("expected", vp), ("inactive", vp), ("ctc_cost", vp), ("ctc_skip", vp), ("posterior", vp),
+                ("real", vp)]
+
+
+MWER_MAX_K = 256
+
 N_PHASES = 6
 
 # name -> (restype, argtypes); every symbol include/sctc.h declares
@@ -275,6 +288,13 @@ PROTOTYPES = {
     "sctc_brnn_ctc_workspace_bytes": (ctypes.c_int, [vp, ctypes.POINTER(Minibatch), ctypes.POINTER(ctypes.c_size_t),
                                                      ctypes.POINTER(ctypes.c_size_t)]),
     "sctc_brnn_set_ctc_workspace": (ctypes.c_int, [vp, vp, ctypes.c_size_t]),
+    "sctc_brnn_mwer_workspace_bytes": (ctypes.c_int, [vp, ctypes.POINTER(Minibatch), ctypes.POINTER(MwerMinibatch),
+                                                      ctypes.POINTER(ctypes.c_size_t)]),
+    "sctc_brnn_set_mwer_workspace": (ctypes.c_int, [vp, vp, ctypes.c_size_t]),
+    "sctc_brnn_mwer_cost_and_grad": (ctypes.c_int, [vp, ctypes.POINTER(Minibatch), ctypes.POINTER(MwerMinibatch),
+                                                    ctypes.c_int32, ctypes.POINTER(MwerOutputs), c_f64p, vp]),
+    "sctc_brnn_mwer_cost_and_grad_async": (ctypes.c_int, [vp, ctypes.POINTER(Minibatch), ctypes.POINTER(MwerMinibatch),
+                                                          ctypes.c_int32, ctypes.POINTER(MwerOutputs), vp]),
     "sctc_brnn_set_profiling": (ctypes.c_int, [vp, ctypes.c_int32]),
     "sctc_brnn_debug_read": (ctypes.c_int, [vp, vp, ctypes.c_int32]),
     "sctc_brnn_debug_buffer": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.POINTER(vp), c_i64p, c_i64p, c_i64p]),

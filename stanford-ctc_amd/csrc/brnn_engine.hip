@@ -10,6 +10,7 @@
 //   contiguous block of rows, and the time-batched GEMMs see N = sum_b T_b frames.
 //   Parameters: tensor i of `stack` at params + offset_i, [rows_p][cols_p], zero padded.
 #include <algorithm>
+#include <cmath>
 #include <numeric>
 #include <vector>
 
@@ -18,6 +19,8 @@
 
 #include <mutex>
 
+#include "brnn_mwer.h"
+#include "brnn_mwer_plan.h"
 #include "ctc_kernels.h"
 #include "elementwise.h"
 #include "gemm_f32.h"
@@ -129,6 +132,12 @@ struct sctc_brnn {
     PinnedStage plan_stage;    // make_plan's uploads
     std::vector<int32_t> ctc_U, ctc_labels;
     std::vector<int64_t> ctc_frame_off, ctc_label_off;
+    // the MWER step (sctc_brnn_mwer_cost_and_grad): caller-owned workspace, staging of its head, the CTC batch's rows
+    void* mwer_ws = nullptr;
+    size_t mwer_ws_bytes = 0;
+    PinnedStage mwer_stage;
+    std::vector<int32_t> mwer_T;
+    std::vector<char> mwer_head;
 };
 
 static int weight_index(const sctc_brnn* h, int layer) { return 2 * layer; }      // W_{layer+1}
@@ -844,6 +853,259 @@ static int run_cost_and_grad(sctc_brnn* h, const sctc_minibatch* mb, int flags, 
     return SCTC_OK;
 }
 
+// ------------------------------------------------------------------ MWER step
+
+// the scalars of the descriptor: no handle, no device
+static int mwer_check_desc(const sctc_mwer_minibatch* mw, const char* what)
+{
+    SCTC_CHECK_ARG(mw, "%s: null MWER descriptor", what);
+    SCTC_CHECK_ARG(mw->K >= 1 && mw->K <= BRNN_MWER_MAX_K, "%s: K = %d hypotheses outside 1..%d", what, mw->K, BRNN_MWER_MAX_K);
+    SCTC_CHECK_ARG(std::isfinite(mw->scale) && mw->scale >= 0.0, "%s: scale %g is not finite or is negative", what, mw->scale);
+    SCTC_CHECK_ARG(std::isfinite(mw->ctc_weight) && mw->ctc_weight >= 0.0, "%s: ctc_weight %g is not finite or is negative", what,
+                   mw->ctc_weight);
+    SCTC_CHECK_ARG(mw->subtract_mean == 0 || mw->subtract_mean == 1, "%s: subtract_mean %d is neither 0 nor 1", what,
+                   mw->subtract_mean);
+    SCTC_CHECK_ARG(mw->K_b && mw->hyp_U && mw->errors, "%s: null field in the MWER descriptor", what);
+    return SCTC_OK;
+}
+
+// What the host knows of an MWER step before anything is queued: the label rows of the CTC batch (rank-major,
+// slot-minor), the head of the workspace and its layout.
+struct MwerHost {
+    std::vector<int32_t> T, U, labels;          // the CTC batch
+    std::vector<int64_t> frame_off, label_off;
+    std::vector<int32_t> src, kb;               // [B * S], [B]: rank order
+    std::vector<double> errors;                 // [B * K] rank order
+    BrnnMwerPlan plan;
+};
+
+static int mwer_prepare(const sctc_brnn* h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, const char* what, MwerHost* out)
+{
+    SCTC_CHECK_ARG(mb && mb->T_b, "%s: null minibatch field", what);
+    SCTC_CHECK_ARG(mb->B >= 1 && mb->B <= h->maxB, "%s: %d utterances, capacity %d", what, mb->B, h->maxB);
+    const int B = mb->B, K = mw->K, A = h->A;
+    const bool with_ref = mw->ctc_weight > 0.0;
+    const int S = K + (with_ref ? 1 : 0);
+    if (with_ref) SCTC_CHECK_ARG(mb->labels && mb->U_b, "%s: ctc_weight > 0 needs the reference labels", what);
+    int64_t N = 0;
+    int Tmax = 0;
+    for (int b = 0; b < B; ++b) {
+        SCTC_CHECK_ARG(mb->T_b[b] >= 1, "%s: utterance %d has no frames", what, b);
+        N += mb->T_b[b];
+        Tmax = std::max(Tmax, mb->T_b[b]);
+    }
+    SCTC_CHECK_ARG(N <= h->maxF, "Batch size exceeds max batch (%lld frames > %lld)", (long long)N, (long long)h->maxF);
+    SCTC_CHECK_ARG(N * S <= INT32_MAX, "%s: N * S = %lld rows do not fit the int32 row index", what, (long long)(N * S));
+    // caller order: which slots are read, where their labels lie
+    std::vector<int64_t> hyp_off((size_t)B * K, -1), ref_off(B, 0);
+    {
+        int64_t at = 0, rat = 0;
+        for (int b = 0; b < B; ++b) {
+            SCTC_CHECK_ARG(mw->K_b[b] >= 0 && mw->K_b[b] <= K, "%s: K_b[%d] = %d outside 0..%d", what, b, mw->K_b[b], K);
+            for (int k = 0; k < mw->K_b[b]; ++k) {
+                const int64_t o = (int64_t)b * K + k;
+                if (!std::isfinite(mw->errors[o])) continue;
+                const int32_t U = mw->hyp_U[o];
+                SCTC_CHECK_ARG(U >= 0, "%s: hypothesis %d of utterance %d has length %d", what, k, b, U);
+                SCTC_CHECK_ARG(U == 0 || mw->hyp_labels, "%s: null hyp_labels", what);
+                for (int i = 0; i < U; ++i)
+                    SCTC_CHECK_ARG(mw->hyp_labels[at + i] >= 1 && mw->hyp_labels[at + i] < A, "%s: label %d of hypothesis %d of "
+                                   "utterance %d is %d, outside [1, %d)", what, i, k, b, mw->hyp_labels[at + i], A);
+                hyp_off[o] = at;
+                at += U;
+            }
+            if (with_ref) {
+                const int32_t U = mb->U_b[b];
+                SCTC_CHECK_ARG(U >= 1, "%s: utterance %d has an empty reference label sequence", what, b);
+                for (int i = 0; i < U; ++i)
+                    SCTC_CHECK_ARG(mb->labels[rat + i] >= 1 && mb->labels[rat + i] < A, "%s: reference label %d of utterance %d is "
+                                   "%d, outside [1, %d)", what, i, b, mb->labels[rat + i], A);
+                ref_off[b] = rat;
+                rat += U;
+            }
+        }
+    }
+    // rank order (make_plan's: by length, descending, stable)
+    std::vector<int> order(B);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return mb->T_b[a] > mb->T_b[b]; });
+    MwerHost& m = *out;
+    m.T.clear(); m.U.clear(); m.labels.clear(); m.frame_off.clear(); m.label_off.clear();
+    m.src.assign((size_t)B * S, BRNN_MWER_SRC_UNREAD);
+    m.kb.assign(B, 0);
+    m.errors.assign((size_t)B * K, 0.0);
+    auto add_row = [&](int r, int s, int T, int U, const int32_t* lab) {
+        m.src[(size_t)r * S + s] = (int32_t)m.T.size();
+        m.T.push_back(T);
+        m.U.push_back(U);
+        m.frame_off.push_back((int64_t)r * S + s);
+        m.label_off.push_back((int64_t)m.labels.size());
+        m.labels.insert(m.labels.end(), lab, lab + U);
+    };
+    for (int r = 0; r < B; ++r) {
+        const int b = order[r];
+        m.kb[r] = mw->K_b[b];
+        for (int k = 0; k < K; ++k) {
+            const int64_t o = (int64_t)b * K + k;
+            m.errors[(size_t)r * K + k] = mw->errors[o];
+            if (hyp_off[o] < 0) continue;
+            if (mw->hyp_U[o] == 0) m.src[(size_t)r * S + k] = BRNN_MWER_SRC_EMPTY;
+            else add_row(r, k, mb->T_b[b], mw->hyp_U[o], mw->hyp_labels + hyp_off[o]);
+        }
+        if (with_ref) add_row(r, K, mb->T_b[b], mb->U_b[b], mb->labels + ref_off[b]);
+    }
+    size_t ctc_bytes = 0;
+    if (!m.T.empty())
+        SCTC_TRY(ctc_workspace_bytes((int)m.T.size(), A, 0, SCTC_F32, m.T.data(), m.U.data(), &ctc_bytes));
+    m.plan = brnn_mwer_plan(B, K, with_ref, A, N, Tmax, ctc_bytes);
+    return SCTC_OK;
+}
+
+static int run_mwer(sctc_brnn* h, const sctc_mwer_minibatch* mw, MwerHost& m, hipStream_t s)
+{
+    const BrnnMwerPlan& pl = m.plan;
+    const int B = pl.B, K = pl.K, S = pl.S;
+    char* const base = static_cast<char*>(h->mwer_ws);
+    // the head: one span, one copy
+    {
+        std::vector<int32_t> rb(pl.Tmax);
+        for (int t = 0; t < pl.Tmax; ++t) rb[t] = h->rowbase[t] * S;
+        char* pin = static_cast<char*>(h->mwer_stage.acquire(pl.head_bytes));
+        h->mwer_head.resize(pin ? 0 : pl.head_bytes);
+        char* host = pin ? pin : h->mwer_head.data();
+        memset(host, 0, pl.head_bytes);
+        memcpy(host + pl.off_errors, m.errors.data(), sizeof(double) * m.errors.size());
+        memcpy(host + pl.off_rowbase, rb.data(), sizeof(int32_t) * rb.size());
+        memcpy(host + pl.off_kb, m.kb.data(), sizeof(int32_t) * m.kb.size());
+        memcpy(host + pl.off_src, m.src.data(), sizeof(int32_t) * m.src.size());
+        PinnedUploadGuard guard(s, true);
+        SCTC_HIP_TRY(hipMemcpyAsync(base, host, pl.head_bytes, hipMemcpyHostToDevice, s));
+        if (pin) {
+            SCTC_HIP_TRY(h->mwer_stage.uploaded(s));
+            guard.done();
+        }       // pageable staging: the guard waits for the copy
+    }
+    auto at = [&](size_t off) { return base + off; };
+    BrnnMwerArgs a;
+    memset(&a, 0, sizeof(a));
+    a.probs = h->probs;
+    a.dlogits = h->dlogits;
+    a.ld = LD(h->Ap);
+    a.kprobs = reinterpret_cast<float*>(at(pl.off_kprobs));
+    a.kgrad = reinterpret_cast<float*>(at(pl.off_kgrad));
+    a.rowbase = h->d_rowbase;
+    a.rowbase_S = reinterpret_cast<const int32_t*>(at(pl.off_rowbase));
+    a.Ts = h->d_Ts;
+    a.kb = reinterpret_cast<const int32_t*>(at(pl.off_kb));
+    a.src = reinterpret_cast<const int32_t*>(at(pl.off_src));
+    a.ctc_cost = reinterpret_cast<const double*>(at(pl.off_ctc_cost));
+    a.ctc_skip = reinterpret_cast<const int32_t*>(at(pl.off_ctc_skip));
+    a.cost = reinterpret_cast<double*>(at(pl.off_cost));
+    a.skip = reinterpret_cast<int32_t*>(at(pl.off_skip));
+    a.ref_cost = reinterpret_cast<double*>(at(pl.off_ref_cost));
+    a.ref_skip = reinterpret_cast<int32_t*>(at(pl.off_ref_skip));
+    a.coef = reinterpret_cast<const double*>(at(pl.off_coef));
+    a.real = reinterpret_cast<const int32_t*>(at(pl.off_real));
+    a.inactive = reinterpret_cast<const int32_t*>(at(pl.off_inactive));
+    a.ctc_weight = mw->ctc_weight;
+    a.B = B; a.K = K; a.S = S; a.A = h->A; a.Tmax = pl.Tmax;
+    SCTC_TRY(launch_brnn_mwer_spread(a, s));
+    if (!m.T.empty()) {
+        sctc_ctc_batch bt;
+        bt.B = (int32_t)m.T.size();
+        bt.A = h->A;
+        bt.blank = 0;
+        bt.dtype = SCTC_F32;
+        bt.ld = pl.ldk;
+        bt.T_b = m.T.data();
+        bt.U_b = m.U.data();
+        bt.frame_off = m.frame_off.data();
+        bt.labels = m.labels.data();
+        bt.label_off = m.label_off.data();
+        bt.rowbase_dev = a.rowbase_S;
+        if (!h->ctc_stage) h->ctc_stage = ctc_new_stage();
+        SCTC_TRY(ctc_run_batch(&bt, a.kprobs, a.kgrad, const_cast<double*>(a.ctc_cost), const_cast<int32_t*>(a.ctc_skip),
+                               at(pl.off_ctc), pl.ctc_bytes, s, h->ctc_stage));
+    }
+    SCTC_TRY(launch_brnn_mwer_empty(a, s));
+    sctc_mwer_config mc;
+    memset(&mc, 0, sizeof(mc));
+    mc.T = pl.Tmax; mc.N = B; mc.K = K; mc.C = h->A;
+    mc.dtype = SCTC_F32;
+    mc.mode = SCTC_TNC_LOGITS;
+    mc.scale = mw->scale;
+    mc.subtract_mean = mw->subtract_mean;
+    SCTC_TRY(sctc_ctc_mwer_coef(&mc, a.cost, a.skip, reinterpret_cast<const double*>(at(pl.off_errors)), h->d_Ts, a.kb,
+                                reinterpret_cast<double*>(at(pl.off_loss)), const_cast<double*>(a.coef),
+                                reinterpret_cast<double*>(at(pl.off_post)), reinterpret_cast<double*>(at(pl.off_expected)),
+                                const_cast<int32_t*>(a.real), const_cast<int32_t*>(a.inactive), s));
+    SCTC_TRY(launch_brnn_mwer_combine(a, s));
+    BrnnMwerResults rs;
+    memset(&rs, 0, sizeof(rs));
+    rs.perm = h->d_perm;
+    rs.loss = reinterpret_cast<const double*>(at(pl.off_loss));
+    rs.expected = reinterpret_cast<const double*>(at(pl.off_expected));
+    rs.post = reinterpret_cast<const double*>(at(pl.off_post));
+    rs.ref_cost = a.ref_cost;
+    rs.inactive = a.inactive;
+    rs.real = a.real;
+    rs.ref_skip = a.ref_skip;
+    rs.out_loss = reinterpret_cast<double*>(at(pl.off_out_loss));
+    rs.out_expected = reinterpret_cast<double*>(at(pl.off_out_expected));
+    rs.out_post = reinterpret_cast<double*>(at(pl.off_out_post));
+    rs.out_ctc_cost = reinterpret_cast<double*>(at(pl.off_out_ctc_cost));
+    rs.out_inactive = reinterpret_cast<int32_t*>(at(pl.off_out_inactive));
+    rs.out_real = reinterpret_cast<int32_t*>(at(pl.off_out_real));
+    rs.out_ctc_skip = reinterpret_cast<int32_t*>(at(pl.off_out_ctc_skip));
+    rs.ctc_weight = mw->ctc_weight;
+    rs.B = B; rs.K = K; rs.with_ref = S > K;
+    return launch_brnn_mwer_results(rs, s);
+}
+
+// forward, the MWER criterion, backward; the outputs go from the workspace's caller-order slices to `out`
+static int run_mwer_cost_and_grad(sctc_brnn* h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, int flags,
+                                  const sctc_mwer_outputs* out, bool out_on_host, hipStream_t s)
+{
+    SCTC_TRY(mwer_check_desc(mw, "brnn_mwer"));
+    SCTC_CHECK_ARG(h, "brnn_mwer: null handle");
+    SCTC_CHECK_ARG(h->cfg.train, "brnn_mwer: model was created with train=0");
+    SCTC_CHECK_ARG(!(flags & SCTC_FLAG_SYNC_SKIP), "brnn_mwer: SCTC_FLAG_SYNC_SKIP does not apply to the MWER step");
+    SCTC_CHECK_ARG(mb && mb->feats_dev, "brnn_mwer: null minibatch field");
+    MwerHost m;
+    SCTC_TRY(mwer_prepare(h, mb, mw, "brnn_mwer", &m));
+    if (m.plan.bytes > h->mwer_ws_bytes || !h->mwer_ws)
+        return set_error(SCTC_ERR_WORKSPACE, "brnn_mwer: workspace %zu bytes < %zu needed (sctc_brnn_set_mwer_workspace)",
+                         h->mwer_ws_bytes, m.plan.bytes);
+    PhaseTimer pt{h, s};
+    if (h->profiling) memset(h->phase_ms, 0, sizeof(h->phase_ms));
+    h->tev_n = 0;
+    SCTC_TRY(make_plan(h, mb, false, s));
+    if (h->TL > 0) SCTC_TRY(recurrent_clear_error(h->counters, s));   // sticky for the whole step
+    SCTC_TRY(run_forward(h, mb, s, pt));      // leaves the timer in SCTC_PHASE_CTC
+    SCTC_TRY(run_mwer(h, mw, m, s));
+    pt.begin(SCTC_PHASE_OTHER);
+    SCTC_TRY(run_backward(h, flags, s, pt));
+    pt.end();
+    if (out) {
+        const BrnnMwerPlan& pl = m.plan;
+        const char* base = static_cast<const char*>(h->mwer_ws);
+        const hipMemcpyKind kind = out_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        const size_t nB = (size_t)pl.B, nBK = (size_t)pl.B * pl.K;
+        auto copy = [&](void* dst, size_t off, size_t bytes) -> int {
+            if (dst) SCTC_HIP_TRY(hipMemcpyAsync(dst, base + off, bytes, kind, s));
+            return SCTC_OK;
+        };
+        SCTC_TRY(copy(out->loss, pl.off_out_loss, nB * sizeof(double)));
+        SCTC_TRY(copy(out->expected, pl.off_out_expected, nB * sizeof(double)));
+        SCTC_TRY(copy(out->inactive, pl.off_out_inactive, nB * sizeof(int32_t)));
+        SCTC_TRY(copy(out->ctc_cost, pl.off_out_ctc_cost, nB * sizeof(double)));
+        SCTC_TRY(copy(out->ctc_skip, pl.off_out_ctc_skip, nB * sizeof(int32_t)));
+        SCTC_TRY(copy(out->posterior, pl.off_out_post, nBK * sizeof(double)));
+        SCTC_TRY(copy(out->real, pl.off_out_real, nBK * sizeof(int32_t)));
+    }
+    return SCTC_OK;
+}
+
 extern "C" {
 
 int sctc_brnn_query(const sctc_brnn_config* cfg, sctc_brnn_sizes* out)
@@ -1251,6 +1513,70 @@ int sctc_brnn_set_ctc_workspace(sctc_brnn_t h, void* workspace_dev, size_t works
     h->ctc_ws_ext = workspace_dev;
     h->ctc_ws_ext_bytes = workspace_bytes;
     return SCTC_OK;
+}
+
+int sctc_brnn_mwer_workspace_bytes(sctc_brnn_t h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, size_t* needed)
+{
+    SCTC_TRY(mwer_check_desc(mw, "brnn_mwer_workspace_bytes"));
+    SCTC_CHECK_ARG(h && needed, "brnn_mwer_workspace_bytes: null argument");
+    SCTC_CHECK_ARG(h->cfg.train, "brnn_mwer_workspace_bytes: the model was created with train = 0");
+    MwerHost m;
+    SCTC_TRY(mwer_prepare(h, mb, mw, "brnn_mwer_workspace_bytes", &m));
+    *needed = m.plan.bytes;
+    return SCTC_OK;
+}
+
+int sctc_brnn_set_mwer_workspace(sctc_brnn_t h, void* workspace_dev, size_t workspace_bytes)
+{
+    SCTC_CHECK_ARG(h, "null handle");
+    SCTC_CHECK_ARG(h->cfg.train, "brnn_set_mwer_workspace: the model was created with train = 0");
+    SCTC_CHECK_ARG((workspace_dev == nullptr) == (workspace_bytes == 0), "brnn_set_mwer_workspace: a buffer and its size, or NULL and 0");
+    SCTC_CHECK_ARG(((uintptr_t)workspace_dev & 255) == 0, "brnn_set_mwer_workspace: the buffer must be 256-byte aligned");
+    h->mwer_ws = workspace_dev;
+    h->mwer_ws_bytes = workspace_bytes;
+    return SCTC_OK;
+}
+
+int sctc_brnn_mwer_cost_and_grad_async(sctc_brnn_t h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, int32_t flags,
+                                       const sctc_mwer_outputs* out_dev, void* stream)
+{
+    return run_mwer_cost_and_grad(h, mb, mw, flags, out_dev, false, (hipStream_t)stream);
+}
+
+static int mwer_cost_and_grad_once(sctc_brnn_t h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, int32_t flags,
+                                   const sctc_mwer_outputs* out_host, double* regcost_host, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    SCTC_TRY(run_mwer_cost_and_grad(h, mb, mw, flags, out_host, true, s));
+    int nw = 0;
+    if (regcost_host && h->cfg.reg > 0.f) {
+        for (size_t i = 0; i < h->tinfo.size(); ++i) {      // as cost_and_grad_once
+            const sctc_tensor_info& t = h->tinfo[i];
+            if (t.kind == 1) continue;
+            SCTC_TRY(launch_sumsq(h->params + t.offset, round_up(t.rows, PAD) * t.ld, h->d_sumsq + nw, h->sumsq_ws, s));
+            ++nw;
+        }
+    }
+    std::vector<double> ss(nw);
+    if (nw) SCTC_HIP_TRY(hipMemcpyAsync(ss.data(), h->d_sumsq, sizeof(double) * nw, hipMemcpyDeviceToHost, s));
+    SCTC_HIP_TRY(hipStreamSynchronize(s));
+    SCTC_TRY(check_recurrent_error(h, s));
+    if (regcost_host) {
+        double rc = 0.0;
+        for (double v : ss) rc += 0.5 * (double)h->cfg.reg * v;
+        *regcost_host = rc;
+    }
+    return SCTC_OK;
+}
+
+int sctc_brnn_mwer_cost_and_grad(sctc_brnn_t h, const sctc_minibatch* mb, const sctc_mwer_minibatch* mw, int32_t flags,
+                                 const sctc_mwer_outputs* out_host, double* regcost_host, void* stream)
+{
+    SCTC_TRY(mwer_check_desc(mw, "brnn_mwer"));
+    SCTC_CHECK_ARG(h, "brnn_mwer: null handle");
+    return with_retry(h, !(flags & SCTC_FLAG_ACCUMULATE), [&]() {
+        return mwer_cost_and_grad_once(h, mb, mw, flags, out_host, regcost_host, stream);
+    });
 }
 
 int sctc_brnn_set_profiling(sctc_brnn_t h, int32_t enable)

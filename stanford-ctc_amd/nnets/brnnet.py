@@ -287,6 +287,176 @@ class NNet:
         self._async_keep = (feats_dev, keep)      # host label arrays / features outlive the launches
         return cost_dev, skip_dev
 
+    # ------------------------------------------------------------------ MWER step
+
+    def _mwer_descriptor(self, B, hyps_list, errors_list, scale, subtract_mean, ctc_weight, K=None, K_b=None):
+        """the sctc_mwer_minibatch of a call and the host arrays it points into.  `K` / `K_b` (tests): more slots
+        than hypotheses are read; hyps_list[b][k] and errors_list[b][k] then exist for every k < K."""
+        if len(hyps_list) != B or len(errors_list) != B:
+            raise ValueError("mwerCostAndGradBatch: %d utterances, %d n-best lists, %d error lists"
+                             % (B, len(hyps_list), len(errors_list)))
+        for name, v in (("scale", scale), ("ctc_weight", ctc_weight)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError("mwerCostAndGradBatch: %s must be a number, not %r" % (name, type(v).__name__))
+            if not np.isfinite(v) or v < 0:
+                raise ValueError("mwerCostAndGradBatch: %s = %r is not finite or is negative" % (name, v))
+        n_b = [len(h) for h in hyps_list]
+        for b in range(B):
+            if len(errors_list[b]) != n_b[b]:
+                raise ValueError("mwerCostAndGradBatch: utterance %d has %d hypotheses and %d errors"
+                                 % (b, n_b[b], len(errors_list[b])))
+        if K is None:
+            K = max([1] + n_b)
+        if not 1 <= K <= _sctc.MWER_MAX_K:
+            raise ValueError("mwerCostAndGradBatch: %d hypotheses outside 1..%d" % (K, _sctc.MWER_MAX_K))
+        K_arr = np.ascontiguousarray(n_b if K_b is None else K_b, dtype=np.int32)
+        U = np.zeros((B, K), dtype=np.int32)
+        W = np.full((B, K), np.nan, dtype=np.float64)
+        labs = [np.zeros(0, dtype=np.int32)]
+        for b in range(B):
+            for k in range(min(n_b[b], K)):
+                row = np.asarray(hyps_list[b][k]).reshape(-1)
+                if row.size and not np.issubdtype(row.dtype, np.integer):
+                    raise TypeError("mwerCostAndGradBatch: hypothesis %d of utterance %d is not an integer sequence" % (k, b))
+                W[b, k] = float(errors_list[b][k])
+                U[b, k] = row.size
+                if k < K_arr[b] and np.isfinite(W[b, k]):      # the slots the contract reads carry labels
+                    labs.append(row.astype(np.int32))
+        lab = np.ascontiguousarray(np.concatenate(labs), dtype=np.int32)
+        if lab.size == 0:
+            lab = np.zeros(1, dtype=np.int32)
+        mw = _sctc.MwerMinibatch(K, _sctc.i32(K_arr), _sctc.i32(lab), _sctc.i32(U), W.ctypes.data_as(_sctc.c_f64p),
+                                 float(scale), 1 if subtract_mean else 0, float(ctc_weight))
+        return mw, K, [K_arr, U, W, lab]
+
+    def _grow_mwer_workspace(self, mb, mw):
+        """the MWER step's workspace (K-fold buffers, CTC scratch of the label rows) is the caller's: kept here, and
+        only ever grown"""
+        torch = _sctc.require_gpu()
+        need = ctypes.c_size_t(0)
+        _sctc.check(_sctc.lib().sctc_brnn_mwer_workspace_bytes(self._h, ctypes.byref(mb), ctypes.byref(mw),
+                                                               ctypes.byref(need)), "mwerCostAndGrad")
+        have = getattr(self, "_mwer_ws", None)
+        if have is None or need.value > have.numel():
+            torch.cuda.synchronize()             # a step that still uses the previous workspace may be in flight
+            ws = torch.empty(need.value + need.value // 8 + 256, dtype=torch.uint8, device="cuda")
+            _sctc.check(_sctc.lib().sctc_brnn_set_mwer_workspace(self._h, ws.data_ptr(), ws.numel()), "mwerCostAndGrad")
+            self._mwer_ws = ws
+
+    def _mwer_setup(self, data_list, hyps_list, errors_list, labels_list, scale, subtract_mean, ctc_weight, accumulate,
+                    feats_dev, T_b, reg_in_grad, K, K_b):
+        if self._h is None:
+            raise RuntimeError("initParams() / fromFile() first")
+        if not self.train:
+            raise ValueError("mwerCostAndGradBatch needs a train=True model")
+        B = len(T_b) if feats_dev is not None else len(data_list)
+        mw, K, keep_w = self._mwer_descriptor(B, hyps_list, errors_list, scale, subtract_mean, ctc_weight, K, K_b)
+        if ctc_weight > 0 and labels_list is None:
+            raise ValueError("mwerCostAndGradBatch: ctc_weight > 0 needs labels_list")
+        if labels_list is not None and len(labels_list) != B:
+            raise ValueError("mwerCostAndGradBatch: %d utterances, %d label rows" % (B, len(labels_list)))
+        if feats_dev is None:
+            T_b = [np.asarray(d).shape[1] for d in data_list]
+            feats_dev = self._stage(data_list)
+        for T in T_b:
+            self.setViews(T)
+        mb, keep = self._minibatch(feats_dev, T_b, labels_list if ctc_weight > 0 else None)
+        self._grow_mwer_workspace(mb, mw)
+        flags = (_sctc.FLAG_ACCUMULATE if accumulate else 0) | (0 if reg_in_grad else _sctc.FLAG_NO_REG_GRAD)
+        return mb, mw, flags, B, K, (feats_dev, keep, keep_w)
+
+    def mwerCostAndGradBatch(self, data_list, hyps_list, errors_list, labels_list=None, scale=1.0, subtract_mean=True,
+                             ctc_weight=0.0, accumulate=False, feats_dev=None, T_b=None, reg_in_grad=True,
+                             return_stats=False, _K=None, _K_b=None):
+        """Minibatch step on the expected error over n-best lists (minimum word error rate training):
+        one forward pass, the CTC recursions of every hypothesis, one backward pass.  hyps_list[b] is a list of integer
+        sequences (labels in [1, outputDim); an empty one is the all-blank hypothesis), errors_list[b] their errors (a
+        non-finite error takes the hypothesis out).  The loss of utterance b is its expected error under the model's
+        posterior over its own list (minus the list's mean error with subtract_mean), plus ctc_weight times the CTC cost
+        of labels_list[b].  Returns (losses float64[B], grad stack, inactive bool[B]) and, with return_stats, a dict of
+        expected [B], posterior [B, K], real [B, K], ctc_cost [B], ctc_skip [B].  The gradient is the SUM over the
+        utterances; reg_in_grad and accumulate as in costAndGradBatch."""
+        mb, mw, flags, B, K, keep = self._mwer_setup(data_list, hyps_list, errors_list, labels_list, scale, subtract_mean,
+                                                     ctc_weight, accumulate, feats_dev, T_b, reg_in_grad, _K, _K_b)
+        loss, expected, ctc_cost = (np.zeros(B, dtype=np.float64) for _ in range(3))
+        inactive, ctc_skip = (np.zeros(B, dtype=np.int32) for _ in range(2))
+        post = np.zeros((B, K), dtype=np.float64)
+        real = np.zeros((B, K), dtype=np.int32)
+        out = _sctc.MwerOutputs(loss.ctypes.data, expected.ctypes.data, inactive.ctypes.data, ctc_cost.ctypes.data,
+                                ctc_skip.ctypes.data, post.ctypes.data, real.ctypes.data)
+        regcost = ctypes.c_double(0.0)
+        rc = _sctc.lib().sctc_brnn_mwer_cost_and_grad(self._h, ctypes.byref(mb), ctypes.byref(mw), flags, ctypes.byref(out),
+                                                      ctypes.byref(regcost), _sctc.current_stream_ptr())
+        _sctc.check(rc, "mwerCostAndGrad")
+        del keep
+        if self.reg > 0:
+            self.regcost = regcost.value
+        res = (loss, self.grad, inactive.astype(bool))
+        if return_stats:
+            res += (dict(expected=expected, posterior=post, real=real.astype(bool), ctc_cost=ctc_cost,
+                         ctc_skip=ctc_skip.astype(bool)),)
+        return res
+
+    def mwerCostAndGradBatchAsync(self, data_list, hyps_list, errors_list, labels_list=None, scale=1.0,
+                                  subtract_mean=True, ctc_weight=0.0, accumulate=False, feats_dev=None, T_b=None,
+                                  reg_in_grad=True):
+        """mwerCostAndGradBatch without a host sync: returns a dict of device tensors (loss, expected, ctc_cost float64
+        [B]; inactive, ctc_skip int32 [B]; posterior float64 [B, K]; real int32 [B, K]).  Call checkAsync() before
+        trusting them."""
+        torch = _sctc.require_gpu()
+        mb, mw, flags, B, K, keep = self._mwer_setup(data_list, hyps_list, errors_list, labels_list, scale, subtract_mean,
+                                                     ctc_weight, accumulate, feats_dev, T_b, reg_in_grad, None, None)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device="cuda")
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device="cuda")
+        res = dict(loss=f64(B), expected=f64(B), inactive=i32(B), ctc_cost=f64(B), ctc_skip=i32(B), posterior=f64(B, K),
+                   real=i32(B, K))
+        out = _sctc.MwerOutputs(*[res[k].data_ptr() for k in ("loss", "expected", "inactive", "ctc_cost", "ctc_skip",
+                                                               "posterior", "real")])
+        rc = _sctc.lib().sctc_brnn_mwer_cost_and_grad_async(self._h, ctypes.byref(mb), ctypes.byref(mw), flags,
+                                                            ctypes.byref(out), _sctc.current_stream_ptr())
+        _sctc.check(rc, "mwerCostAndGrad")
+        self._async_keep = keep
+        return res
+
+    def nbestBatch(self, data_list, refs_list, nbest, beam=40, unit="word", space=None, lm=None, alpha=1.0, beta=0.0):
+        """The n-best lists and their errors that mwerCostAndGradBatch takes, from the prefix beam search on the
+        model's own output, through existing calls only: forwardDevice(log=True), ctc_fast.decode_beam_batch(nbest=),
+        the ranks whose score is -inf dropped, errors against refs_list from ctc_fast.edit_distance_batch
+        (unit="char") or ctc_fast.word_errors_batch (unit="word", `space` required).  Returns (hyps_list, errors_list):
+        per utterance a list of int32 arrays and a float64 array.  No gradient is touched."""
+        import ctc_fast
+        if unit not in ("char", "word"):
+            raise ValueError("nbestBatch: unit must be 'char' or 'word', not %r" % (unit,))
+        K = int(nbest)
+        if not 1 <= K <= _sctc.MWER_MAX_K:
+            raise ValueError("nbestBatch: nbest = %d outside 1..%d" % (K, _sctc.MWER_MAX_K))
+        if unit == "word" and (space is None or not 1 <= int(space) < self.outputDim):
+            raise ValueError("nbestBatch: the word unit needs the space symbol, in [1, %d)" % self.outputDim)
+        B = len(data_list)
+        if len(refs_list) != B:
+            raise ValueError("nbestBatch: %d references for %d utterances" % (len(refs_list), B))
+        refs = [np.ascontiguousarray(np.asarray(r).reshape(-1), dtype=np.int32) for r in refs_list]
+        lp, T_b = self.forwardDevice(data_list, log=True)
+        rows, scores = ctc_fast.decode_beam_batch(lp, [int(t) for t in T_b], beam=beam, alpha=alpha, beta=beta, lm=lm,
+                                                  nbest=K)
+        if K == 1:
+            rows, scores = [[r] for r in rows], np.asarray(scores).reshape(B, 1)
+        hyps = [[np.asarray(rows[b][k], dtype=np.int32) for k in range(K) if scores[b, k] != float("-inf")]
+                for b in range(B)]
+        flat = [h for row in hyps for h in row]
+        owner = [b for b, row in enumerate(hyps) for _ in row]
+        errors = [np.zeros(len(row), dtype=np.float64) for row in hyps]
+        if flat:
+            if unit == "char":
+                dist = ctc_fast.edit_distance_batch(refs, flat, a_index=owner)[:, 0]
+            else:
+                dist = ctc_fast.word_errors_batch([refs[b] for b in owner], flat, int(space), A=self.outputDim)[:, 0]
+            at = 0
+            for b, row in enumerate(hyps):
+                errors[b][:] = dist[at:at + len(row)]
+                at += len(row)
+        return hyps, errors
+
     # ------------------------------------------------------------------ one utterance per stream
 
     def _lanes_for(self, n_streams):

@@ -64,6 +64,14 @@ def build_parser():
     p.add_argument("--anneal", type=float, default=1.3)
     p.add_argument("--reg", type=float, default=0.0)
     p.add_argument("--minibatch", type=int, default=1, help="utterances per step (reference: 1)")
+    p.add_argument("--criterion", choices=("ctc", "mwer"), default="ctc",
+                   help="mwer: expected error over the model's own n-best lists (DESIGN.md 4.17)")
+    p.add_argument("--mwer_nbest", type=int, default=4)
+    p.add_argument("--mwer_beam", type=int, default=40)
+    p.add_argument("--mwer_unit", choices=("char", "word"), default="word")
+    p.add_argument("--mwer_space", type=int, default=None, help="id of the space symbol (word unit)")
+    p.add_argument("--mwer_scale", type=float, default=1.0)
+    p.add_argument("--mwer_ctc_weight", type=float, default=0.0)
     # data
     p.add_argument("--dataDir", default="./")
     p.add_argument("--alisDir", default=None)
@@ -198,7 +206,10 @@ def run(args=None):
     nn = rnnet.NNet(o.inputDim, o.outputDim, o.layerSize, o.numLayers, o.maxUttLen,
                     temporalLayer=o.temporalLayer, reg=o.reg, maxUtts=max(1, o.minibatch))
     nn.initParams()
-    opt = sgd.SGD(nn, o.maxUttLen, alpha=o.step, momentum=o.momentum, minibatch=o.minibatch)
+    mwer = dict(nbest=o.mwer_nbest, beam=o.mwer_beam, unit=o.mwer_unit, space=o.mwer_space, scale=o.mwer_scale,
+                ctc_weight=o.mwer_ctc_weight) if o.criterion == "mwer" else None
+    opt = sgd.SGD(nn, o.maxUttLen, alpha=o.step, momentum=o.momentum, minibatch=o.minibatch, criterion=o.criterion,
+                  mwer=mwer)
     cfg["param_count"] = int(nn._param_count)
     if master:
         with open(cfg["cfg_file"], "w") as f:

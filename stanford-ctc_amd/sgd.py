@@ -14,6 +14,9 @@ Extensions (off by default, reference behaviour is ``minibatch=1`` on one GPU):
 ``minibatch=N`` processes N utterances per step through ``costAndGradBatch`` and, under
 ``torch.distributed``, shards them over the ranks and all-reduces the gradient
 (mean over non-skipped utterances, ctc/nnet.py:106-124 convention; dist_sgd.py).
+``criterion="mwer"`` trains on the expected error over the model's own n-best lists (DESIGN.md
+§4.17): a step is ``NNet.nbestBatch`` followed by ``NNet.mwerCostAndGradBatch`` at the
+look-ahead point, on one GPU.
 """
 import logging
 import pickle
@@ -40,10 +43,23 @@ def lattice_fits(T, U, max_frames):
     return (T + 2) * w <= (max_frames + 2) * LATTICE_STATES_RESERVED
 
 
+MWER_DEFAULTS = dict(nbest=4, beam=40, unit="word", space=None, lm=None, alpha=1.0, beta=0.0, scale=1.0, ctc_weight=0.0)
+
+
 class SGD:
 
     def __init__(self, model, maxBatch, alpha=1e-2, optimizer='nesterov',
-                 momentum=0.9, maxGradNorm=1500, minibatch=1):
+                 momentum=0.9, maxGradNorm=1500, minibatch=1, criterion="ctc", mwer=None):
+        if criterion not in ("ctc", "mwer"):
+            raise ValueError("criterion must be 'ctc' or 'mwer', not %r" % (criterion,))
+        self.criterion = criterion
+        # nbest, beam, unit, space, lm, alpha, beta: NNet.nbestBatch; scale, ctc_weight: NNet.mwerCostAndGradBatch
+        self.mwer = dict(MWER_DEFAULTS)
+        unknown = set(mwer or {}) - set(MWER_DEFAULTS)
+        if unknown:
+            raise ValueError("unknown mwer option(s): %s" % ", ".join(sorted(unknown)))
+        self.mwer.update(mwer or {})
+        self.last_expected = None       # mean expected error of the last MWER step's contributing utterances
         self.model = model
         self.maxBatch = maxBatch
         self.it = 0
@@ -197,13 +213,29 @@ class SGD:
         m = self.model
         # minibatch / data-parallel: the engine returns the SUM of the data gradients; the L2
         # term enters once, after the all-reduce and the 1/n_valid scaling (_grad_sumsq/_apply)
-        reference_mode = len(batch) == 1 and world == 1
+        if self.criterion == "mwer" and world > 1:
+            raise ValueError("criterion='mwer' runs on one GPU (data-parallel MWER is not built)")
+        reference_mode = len(batch) == 1 and world == 1 and self.criterion == "ctc"
         reg_late = 0.0 if reference_mode else float(m.reg)
         # w = w + mom*velocity (evaluate gradient at future point), sgd.py:91-93
         m.updateParams(mom, self.velocity)
         cost_dev = skip_dev = regc = None
         try:
-            if reference_mode:
+            if self.criterion == "mwer":
+                o = self.mwer
+                datas, refs = [d for _, d, _ in local], [l for _, _, l in local]
+                hyps, errs = m.nbestBatch(datas, refs, o["nbest"], beam=o["beam"], unit=o["unit"], space=o["space"],
+                                          lm=o["lm"], alpha=o["alpha"], beta=o["beta"])
+                costs, grad, inactive, stats = m.mwerCostAndGradBatch(
+                    datas, hyps, errs, labels_list=refs if o["ctc_weight"] > 0 else None, scale=o["scale"],
+                    ctc_weight=o["ctc_weight"], reg_in_grad=False, return_stats=True)
+                # an utterance contributed when it was active or its reference term entered
+                ref_ok = (~stats["ctc_skip"]) & np.isfinite(stats["ctc_cost"]) if o["ctc_weight"] > 0 \
+                    else np.zeros(len(local), dtype=bool)
+                skips = inactive & ~ref_ok
+                if (~inactive).any():
+                    self.last_expected = float(stats["expected"][~inactive].mean())
+            elif reference_mode:
                 k, data, labels = batch[0]
                 cost, grad, skip = m.costAndGrad(data, labels)
                 if m.reg > 0:
