@@ -966,6 +966,10 @@ int sctc_brnn_check(sctc_brnn_t h, void* stream);
  * step re-run after SCTC_ERR_TIMEOUT, SCTC_REC_VARIANT=3), 0 = none yet; *retries = steps of this
  * handle that were re-run after a timeout.  Any pointer may be NULL. */
 int sctc_brnn_recurrent_path(sctc_brnn_t h, int32_t* forward_path, int32_t* bptt_path, int32_t* retries);
+/* the order the last backward pass of the handle ran in (read-only; diagnostics / tests): 0 = serial, 1 = the weight
+ * gradients above the temporal layer beside the default BPTT grid, 2 = beside the half-grid BPTT (SCTC_BWD_OVERLAP,
+ * INTEGRATION.md); negative: null handle */
+int sctc_brnn_bwd_overlap_mode(sctc_brnn_t h);
 
 /* NNet(train=False).costAndGrad(data) (brnnet.py:171-173): probs_dev float [sum T][output_dim],
  * caller order, each utterance the reference's (outputDim,T) F-order probs */

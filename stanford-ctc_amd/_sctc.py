@@ -282,6 +282,7 @@ PROTOTYPES = {
                                                      ctypes.c_int32, vp, vp, vp]),
     "sctc_brnn_check": (ctypes.c_int, [vp, vp]),
     "sctc_brnn_recurrent_path": (ctypes.c_int, [vp, c_i32p, c_i32p, c_i32p]),
+    "sctc_brnn_bwd_overlap_mode": (ctypes.c_int, [vp]),
     "sctc_brnn_grad_event": (vp, [vp, ctypes.c_int32]),
     "sctc_stream_wait_event": (ctypes.c_int, [vp, vp]),
     "sctc_brnn_forward": (ctypes.c_int, [vp, ctypes.POINTER(Minibatch), vp, vp]),

@@ -20,6 +20,7 @@
 #include <mutex>
 
 #include "brnn_mwer.h"
+#include "bwd_overlap_plan.h"
 #include "brnn_mwer_plan.h"
 #include "ctc_kernels.h"
 #include "elementwise.h"
@@ -69,6 +70,12 @@ struct sctc_brnn {
     float *Z, *hF, *hB;       // temporal layer: pre-activation, forward / backward states
     float *logits, *probs, *dlogits;
     float *dA, *dBuf, *dF, *dBk;  // deltas: ping-pong pair + recurrent pair
+    // the overlap order of the backward pass (bwd_overlap_plan.h): n_dx extra delta buffers; the stream the weight gradients
+    // beside the BPTT run on, forked off the step's stream in front of the BPTT launch and joined behind it
+    float* dX[BWD_MAX_EXTRA] = {};
+    int n_dx = 0;
+    hipStream_t ov_stream = nullptr;
+    hipEvent_t ov_fork = nullptr, ov_join = nullptr;
     // 16-bit shadow copies (operand_dtype = SCTC_F16 only; nullptr otherwise): f = float16 (forward
     // operands), b = bfloat16 (backward operands).  Written by the producer of the fp32 matrix.
     std::vector<uint16_t*> act16f, act16b;      // [NL + 1], shadows of act[i]
@@ -123,6 +130,11 @@ struct sctc_brnn {
     int rec_poll_delay = -1;   // env SCTC_REC_POLL_DELAY (s_sleep units before a step's first poll; default by layer size)
     int rec_variant = REC_V_AUTO;   // env SCTC_REC_VARIANT: a RecVariant (recurrent_plan.h)
     int rec_force_fallback = 0;   // set while a timed-out step is retried on the per-step fallback
+    int rec_retrying = 0;         // set while a timed-out step is retried at all: the serial backward order
+    int bwd_overlap = BWD_OVERLAP_DEFAULT;  // env SCTC_BWD_OVERLAP: a BwdOverlapMode
+    int bwd_overlap_last = 0;     // the BwdOverlapMode the last backward pass ran in
+    hipEvent_t ov_ev[2] = {};     // profiling 2: start / end of the weight gradients beside the BPTT, on their stream
+    bool ov_timed = false;        // the last backward pass recorded them
     int rec_path[2] = {0, 0};     // REC_PATH_* of the last forward / BPTT recurrence
     int rec_retries = 0;          // steps of this handle that were re-run after SCTC_ERR_TIMEOUT
     const float* last_delta1 = nullptr;   // delta entering layer 1 (A operand of the dW1 GEMM) of the last backward pass
@@ -204,6 +216,22 @@ static void build_tensor_table(const Dims& d, std::vector<sctc_tensor_info>* t, 
     *count = cnt;
 }
 
+// SCTC_BWD_OVERLAP as a BwdOverlapMode (unset: the measured default), BWD_OVERLAP_OFF on a device without stream memory
+// waits (what holds the stream of the gradients beside the BPTT until its grid is resident).  Asked by the workspace
+// query, by carve and by create, which must agree: the switch is not to change between a handle's query and its creation.
+static int bwd_overlap_wanted()
+{
+    int mode = BWD_OVERLAP_DEFAULT;
+    if (const char* ov = getenv("SCTC_BWD_OVERLAP")) mode = atoi(ov) == 1 ? BWD_OVERLAP_CLAIM : (atoi(ov) == 2 ? BWD_OVERLAP_HALF : BWD_OVERLAP_OFF);
+    if (mode == BWD_OVERLAP_OFF) return mode;
+    int dev = 0, can = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        can = 0;
+    }
+    return can ? mode : BWD_OVERLAP_OFF;
+}
+
 // lays the workspace out; with h == nullptr only measures
 static size_t carve(const sctc_brnn_config* c, const Dims& d, sctc_brnn* h, void* ws, size_t bytes)
 {
@@ -227,6 +255,11 @@ static size_t carve(const sctc_brnn_config* c, const Dims& d, sctc_brnn* h, void
         dBuf = f(F * LD(d.Hp));
         if (d.TL > 0) { dF = f(F * LD(d.Hp)); dBk = f(F * LD(d.Hp)); }
     }
+    // (only where the overlap order can run at all: switched on, and the device has stream memory waits)
+    const int n_dx = Bm >= 17 && bwd_overlap_wanted() != BWD_OVERLAP_OFF
+                         ? bwd_overlap_extra_bufs(d.NL, d.TL, d.Hp, c->operand_dtype == SCTC_F32, c->train != 0) : 0;
+    float* dX[BWD_MAX_EXTRA] = {};
+    for (int k = 0; k < n_dx; ++k) dX[k] = f(F * LD(d.Hp));
     // 16-bit shadows
     const bool h16 = c->operand_dtype == SCTC_F16;
     std::vector<uint16_t*> act16f(d.NL + 1, nullptr), act16b(d.NL + 1, nullptr), WT16b(d.NL + 1, nullptr);
@@ -296,6 +329,8 @@ static size_t carve(const sctc_brnn_config* c, const Dims& d, sctc_brnn* h, void
         h->d_idx_lo = d_idx_lo; h->d_idx_hi = d_idx_hi; h->d_perm = d_perm; h->d_xbase = d_xbase;
         h->ctc_ws = ctc_ws; h->ctc_ws_bytes = ctc_bytes;
         h->splitk_ws = splitk_ws; h->splitk_floats = sk;
+        h->n_dx = n_dx;
+        for (int k = 0; k < BWD_MAX_EXTRA; ++k) h->dX[k] = dX[k];
         h->xbuf = xbuf; h->counters = counters; h->rec_debug = rec_debug;
         h->act16f = act16f; h->act16b = act16b; h->WT16b = WT16b; h->W16f = W16f;
         h->hF16b = hF16b; h->hB16b = hB16b; h->dF16b = dF16b; h->dBk16b = dBk16b;
@@ -461,6 +496,45 @@ static int launch_gemm(const sctc_brnn* h, GemmArgs& g, hipStream_t s)
     return launch_gemm_f32(g, s);
 }
 
+// The order the next backward pass of the handle runs in (bwd_overlap_plan.h).  The serial order whenever the BPTT launch
+// might not be ONE persistent grid that leaves the GEMMs CUs of their own: a retried step, shared-device mode (the launch is
+// synchronous under the lease), a forced recurrent variant; and under the synchronising phase timers.
+static int bwd_overlap_mode(const sctc_brnn* h)
+{
+    if (h->bwd_overlap == BWD_OVERLAP_OFF || h->n_dx == 0 || !h->ov_stream || h->Tmax < 2) return BWD_OVERLAP_OFF;
+    if (!bwd_overlap_eligible(h->NL, h->TL, h->Hp, h->cfg.operand_dtype == SCTC_F32, h->cfg.train != 0, h->B)) return BWD_OVERLAP_OFF;
+    if (h->rec_variant != REC_V_AUTO || h->rec_force_fallback || h->rec_retrying || h->profiling == 1 ||
+        recurrent_shared_device_mode())
+        return BWD_OVERLAP_OFF;
+    return h->bwd_overlap;
+}
+
+// The weight gradients held back for the BPTT launch (RecBeside): queued on the handle's own stream, which is forked off the
+// step's stream here -- every operand is final, the step flags are zero -- and held until both directions' grids are resident.
+// They share the step's split-K workspace: nothing on the step's stream uses it between the fork and the join.
+struct HeldGemms {
+    sctc_brnn* h;
+    hipStream_t s;
+    std::vector<GemmArgs> g;
+    bool timed, forked;
+};
+static int launch_held_beside(void* ctx)
+{
+    HeldGemms* hg = static_cast<HeldGemms*>(ctx);
+    sctc_brnn* h = hg->h;
+    SCTC_HIP_TRY(hipEventRecord(h->ov_fork, hg->s));
+    SCTC_HIP_TRY(hipStreamWaitEvent(h->ov_stream, h->ov_fork, 0));
+    // from here on the other stream may hold a memory wait: whatever fails below, run_backward sets the words (`forked`)
+    hg->forked = true;
+    for (int g = 0; g < 2; ++g)
+        SCTC_HIP_TRY(hipStreamWaitValue32(h->ov_stream, rec_resident_word(h->counters, g), 2, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    if (hg->timed) SCTC_HIP_TRY(hipEventRecord(h->ov_ev[0], h->ov_stream));
+    for (GemmArgs& g : hg->g) SCTC_TRY(launch_gemm(h, g, h->ov_stream));
+    if (hg->timed) SCTC_HIP_TRY(hipEventRecord(h->ov_ev[1], h->ov_stream));
+    SCTC_HIP_TRY(hipEventRecord(h->ov_join, h->ov_stream));
+    return SCTC_OK;
+}
+
 static const float* tensor_ptr(const sctc_brnn* h, const float* base, int idx)
 {
     return base + h->tinfo[idx].offset;
@@ -614,8 +688,10 @@ static int with_retry(sctc_brnn* h, bool retry_ok, Step step)
                     attempt == 0 ? "under the device lease" : "on the per-step fallback");
         ++h->rec_retries;
         h->rec_force_fallback = attempt == 1;
+        h->rec_retrying = 1;
         rc = step();
         h->rec_force_fallback = 0;
+        h->rec_retrying = 0;
     }
     return rc;
 }
@@ -683,8 +759,16 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
     const float* d_in = h->dlogits;
     const uint16_t* d_in16 = h->dlogits16;
     int d_in_ld = LD(h->Ap);
-    float* bufs[2] = {h->dA, h->dBuf};
-    uint16_t* bufs16[2] = {h->dA16, h->dBuf16};
+    // Which delta buffer every GEMM writes and reads, and which weight gradients wait for the BPTT grid (bwd_overlap_plan.h)
+    const int ov = bwd_overlap_mode(h);
+    h->bwd_overlap_last = ov;
+    h->ov_timed = false;
+    BwdRoute route;
+    if (!bwd_route(h->NL, h->TL, ov != BWD_OVERLAP_OFF, &route)) return set_error(SCTC_ERR_ARG, "brnn: no delta buffer route for %d layers", h->NL);
+    const auto delta_buf = [&](int b) { return b == BWD_BUF_A ? h->dA : (b == BWD_BUF_B ? h->dBuf : h->dX[b - BWD_BUF_X0]); };
+    // (16-bit operands always take the serial order: the extra buffers have no 16-bit twin)
+    const auto delta_buf16 = [&](int b) { return b == BWD_BUF_A ? h->dA16 : (b == BWD_BUF_B ? h->dBuf16 : (uint16_t*)nullptr); };
+    HeldGemms held = {h, s, {}, false, false};
     if (h16) {
         SCTC_TRY(launch_cvt16(h->dlogits, nullptr, h->dlogits16, N * LD(h->Ap), s));
         for (int l = 1; l <= h->NL; ++l) {        // W^T as the K-contiguous B operand of the delta GEMMs
@@ -693,7 +777,6 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
             SCTC_TRY(launch_transpose_bf16(h->params + wl.offset, LD(h->Hp), h->WT16b[l], LD(outp), outp, h->Hp, s));
         }
     }
-    int which = 0;
     bool fused_sum = false;   // the sum of the two BPTT outputs is left to the next weight gradient (native fp32 only)
     for (int i = h->NL; i >= 0; --i) {          // brnnet.py:191-243
         pt.begin(SCTC_PHASE_BWD_GEMM);
@@ -724,9 +807,17 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
                 g.A = reinterpret_cast<const float*>(d_in16);
                 g.B = reinterpret_cast<const float*>(h->act16b[i]);
             }
-            SCTC_TRY(launch_gemm(h, g, s));
+            if (route.deferred[i]) {
+                // Held back until the BPTT grid is resident.  It reads d_in (loop index NL: the CTC gradient; NL - 1: dA; NL - 2:
+                // dBuf; then dX[0], dX[1], ...) and act[i]: final here, and no launch in front of the join writes them -- the
+                // delta GEMMs below write dA, dBuf, dX[0], ... in turn, the BPTT dF / dBk.
+                held.g.push_back(g);
+            } else {
+                SCTC_TRY(launch_gemm(h, g, s));
+            }
             // The weight gradients of the layers above the temporal layer (loop indices i >= TL: W_{TL+1}
-            // .. W_{NL+1}) finish BEFORE the BPTT recurrence starts.  A collective
+            // .. W_{NL+1}) finish BEFORE the BPTT recurrence starts in the serial order, and while it runs in the
+            // overlap order.  A collective
             // started on their event would hold compute units while the persistent BPTT grid is being
             // placed (all of its workgroups must be resident at once; the two-chain kernel takes every
             // register of 200 CUs and half of the other 56): their events are recorded after BPTT has retired instead (below), so a
@@ -737,7 +828,8 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
         if (i == 0) break;
         pt.begin(SCTC_PHASE_BWD_GEMM);
         // deltasOut = W^T deltasIn, brnnet.py:204  (+ sign(hActs[i]) mask, :235-237)
-        float* d_out = bufs[which];
+        float* d_out = delta_buf(route.d_out[i]);
+        uint16_t* d_out16 = delta_buf16(route.d_out[i]);
         {
             // A = d_in [N][outp], K = outp; B(k=out, n=in) = W[out][in]
             GemmArgs g = gemm_args({d_in, d_in_ld, 1}, {W, LD(inp), 0}, N, inp, outp, d_out, LD(inp), bprec);
@@ -748,7 +840,7 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
                 g.B = reinterpret_cast<const float*>(h->WT16b[i]);   // B(k = out, n = in) = W^T[in][out]
                 g.ldb = LD(outp);
                 g.b_kcontig = 1;
-                g.C16b = bufs16[which];
+                g.C16b = d_out16;
                 g.ldc16 = LD(inp);
                 if (i != h->TL) {
                     // the layer's activations exist as 16-bit shadows only (run_forward): the mask is their
@@ -763,16 +855,46 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
             SCTC_TRY(launch_gemm(h, g, s));
         }
         if (i == h->TL) {
-            pt.begin(SCTC_PHASE_BWD_REC);
-            const RecArgs r = rec_args(h, true, d_out);
-            SCTC_TRY(launch_recurrent(r, s, &h->rec_path[1]));
+            RecArgs r = rec_args(h, true, d_out);
+            if (ov == BWD_OVERLAP_OFF) {
+                pt.begin(SCTC_PHASE_BWD_REC);
+                SCTC_TRY(launch_recurrent(r, s, &h->rec_path[1]));
+            } else {
+                // The held weight gradients run on the handle's own stream, which waits until every BPTT workgroup is resident
+                // (placed first, the GEMM blocks would be back-filled and the persistent grid would wait for the whole GEMM
+                // grid); the grid's LDS claim keeps them off its CUs.  The step's stream joins behind the BPTT.
+                // Asynchronous timers: the BPTT by the step's events as ever, the gradients beside it by events on their own
+                // stream; what the join waits for beyond the BPTT is left out of the step's events (it is part of the latter).
+                held.timed = h->profiling == 2 && h->ov_ev[0];
+                pt.begin(SCTC_PHASE_BWD_REC);
+                r.variant = ov == BWD_OVERLAP_HALF ? REC_V_T_HALF : REC_V_T_CLAIM;
+                RecBeside beside = {launch_held_beside, &held, 0};
+                const int rc = launch_recurrent(r, s, &h->rec_path[1], &beside);
+                if (held.forked) {
+                    // (anything that failed behind the fork -- queueing the waits or the gradients, the BPTT launch: the words are
+                    // set from here, the other stream must not wait for ever; the step fails with rc)
+                    if (rc != SCTC_OK)
+                        for (int g = 0; g < 2; ++g) (void)hipMemsetD32Async((hipDeviceptr_t)rec_resident_word(h->counters, g), 2, 1, s);
+                    if (h->profiling == 2) pt.mark(-1);
+                    const hipError_t je = hipStreamWaitEvent(s, h->ov_join, 0);
+                    if (rc == SCTC_OK) SCTC_HIP_TRY(je);
+                    h->ov_timed = held.timed && rc == SCTC_OK;
+                }
+                SCTC_TRY(rc);
+                pt.begin(SCTC_PHASE_BWD_GEMM);
+                if (!held.forked) {
+                    // the BPTT did not run as one grid of that kind (device lease, per-step fallback): the serial order after all
+                    for (GemmArgs& g : held.g) SCTC_TRY(launch_gemm(h, g, s));
+                    h->bwd_overlap_last = BWD_OVERLAP_OFF;
+                }
+            }
             for (int l = h->NL; l >= h->TL; --l)     // the held-back events of the layers above (see there)
                 SCTC_HIP_TRY(hipEventRecord(h->grad_ev[weight_index(h, l)], s));
             pt.begin(SCTC_PHASE_BWD_GEMM);
             // deltasOut = deltasFor + deltasBack, brnnet.py:233 -- in the fp16 configuration first, in the
             // pass that also writes the bfloat16 copies of dF / dBk (A operands of the recurrent weight
             // gradient); its fp32 sum has no reader (the delta GEMM below takes the bfloat16 shadow)
-            if (h16) SCTC_TRY(launch_add16(nullptr, h->dF, h->dBk, nullptr, bufs16[which], N * LD(h->Hp), s,
+            if (h16) SCTC_TRY(launch_add16(nullptr, h->dF, h->dBk, nullptr, d_out16, N * LD(h->Hp), s,
                                            h->dF16b, h->dBk16b));
             // dwtf = deltasFor[:,1:T] . hActsFor[:,0:T-1]^T ; dwtb = deltasBack[:,0:T-1] . hActsBack[:,1:T]^T
             // (brnnet.py:227-230) over the (lo = frame t, hi = frame t+1) row pairs of every utterance
@@ -815,9 +937,8 @@ static int run_backward(sctc_brnn* h, int flags, hipStream_t s, PhaseTimer& pt)
             }
         }
         d_in = d_out;
-        d_in16 = bufs16[which];
+        d_in16 = d_out16;
         d_in_ld = LD(h->Hp);
-        which ^= 1;
     }
     h->last_delta1 = d_in;
     h->last_delta1_16 = h16 ? d_in16 : nullptr;
@@ -1169,6 +1290,17 @@ int sctc_brnn_create(const sctc_brnn_config* cfg, float* params_dev, float* grad
     const char* pd = getenv("SCTC_REC_POLL_DELAY");
     h->rec_poll_delay = pd ? atoi(pd) : -1;
     if (const char* fa = getenv("SCTC_FUSE_ADD")) h->fuse_add = atoi(fa) != 0;
+    h->bwd_overlap = bwd_overlap_wanted();
+    if (h->bwd_overlap != BWD_OVERLAP_OFF && h->n_dx > 0) {
+        // the stream of the gradients beside the BPTT: without it the serial order
+        if (hipStreamCreateWithFlags(&h->ov_stream, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&h->ov_fork, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&h->ov_join, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h->ov_stream) (void)hipStreamDestroy(h->ov_stream);
+            h->ov_stream = nullptr;
+        }
+    }
     const char* dbg = getenv("SCTC_REC_DEBUG");
     h->rec_debug_on = dbg ? atoi(dbg) : 0;
     *out = h;
@@ -1188,6 +1320,12 @@ int sctc_brnn_destroy(sctc_brnn_t h)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->tev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->ov_ev[0], h->ov_ev[1], h->ov_fork, h->ov_join})
+        if (e) (void)hipEventDestroy(e);
+    if (h->ov_stream) {
+        (void)hipStreamSynchronize(h->ov_stream);
+        (void)hipStreamDestroy(h->ov_stream);
+    }
     delete h;
     return SCTC_OK;
 }
@@ -1417,6 +1555,8 @@ int sctc_device_pci_bus_id(int32_t device, char* out, int32_t out_len)
     return SCTC_OK;
 }
 
+int sctc_brnn_bwd_overlap_mode(sctc_brnn_t h) { return h ? h->bwd_overlap_last : -1; }
+
 int sctc_brnn_recurrent_path(sctc_brnn_t h, int32_t* forward_path, int32_t* bptt_path, int32_t* retries)
 {
     SCTC_CHECK_ARG(h, "brnn_recurrent_path: null handle");
@@ -1592,6 +1732,7 @@ int sctc_brnn_set_profiling(sctc_brnn_t h, int32_t enable)
     if (enable == 2 && h->tev.empty()) {
         h->tev.resize(128);
         for (hipEvent_t& e : h->tev) SCTC_HIP_TRY(hipEventCreate(&e));
+        for (hipEvent_t& e : h->ov_ev) SCTC_HIP_TRY(hipEventCreate(&e));
     }
     h->profiling = enable == 2 ? 2 : (enable ? 1 : 0);
     h->tev_n = 0;
@@ -1611,6 +1752,13 @@ int sctc_brnn_phase_ms(sctc_brnn_t h, float* ms_out)
             float ms = 0.f;
             SCTC_HIP_TRY(hipEventElapsedTime(&ms, h->tev[i], h->tev[i + 1]));
             h->phase_ms[h->tev_phase[i]] += ms;
+        }
+        // the overlap order: the weight gradients beside the BPTT, by the events on their own stream.  They ran WHILE the BPTT
+        // did: the phases then add up to more than the step took, by the time the two overlapped
+        if (h->ov_timed) {
+            float gemm = 0.f;
+            SCTC_HIP_TRY(hipEventElapsedTime(&gemm, h->ov_ev[0], h->ov_ev[1]));
+            h->phase_ms[SCTC_PHASE_BWD_GEMM] += gemm;
         }
     }
     memcpy(ms_out, h->phase_ms, sizeof(h->phase_ms));

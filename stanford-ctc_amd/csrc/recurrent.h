@@ -75,7 +75,21 @@ static constexpr int REC_PATH_NONE = 0;
 static constexpr int REC_PATH_PERSISTENT = 1;          // one whole-device persistent launch per pass
 static constexpr int REC_PATH_PERSISTENT_LEASED = 2;   // the same under the inter-process device lease
 static constexpr int REC_PATH_FALLBACK = 3;            // one launch per time step (no spinning)
-int launch_recurrent(const RecArgs& a, hipStream_t stream, int* path = nullptr);
+// Work of the caller's that runs on ANOTHER stream beside a persistent grid (REC_V_T_HALF / REC_V_T_CLAIM: a grid that
+// leaves a GEMM block no LDS on its CUs).  fn(ctx) is called at most once, directly in front of the grid's launch -- the step
+// flags are zero on `stream` by then -- and only for such a grid launched through the in-process gate: not under the device
+// lease, not on the per-step fallback, not for a minibatch cut into several launches (`called` stays 0).  It forks the other
+// stream off `stream` and holds it (hipStreamWaitValue32) until rec_resident_word(counters, g), g = 0, 1, are >= 2.
+struct RecBeside {
+    int (*fn)(void* ctx);
+    void* ctx;
+    int called;
+};
+// The tiled kernel's step flag of chain (direction g, sub-chain A), producer 0: j + 1 once its step j is published.  Step 1 is
+// computed from the step-0 results of EVERY producer of the chain, and every workgroup of direction g is one: the word reaches
+// 2 (the minibatch's longest utterance has >= 2 frames) only after all workgroups of that direction have become resident.
+static inline unsigned* rec_resident_word(unsigned* counters, int g) { return counters + 32 + (size_t)(g * 2 * 64) * REC_FLAG_STRIDE; }
+int launch_recurrent(const RecArgs& a, hipStream_t stream, int* path = nullptr, RecBeside* beside = nullptr);
 // clears the sticky error word (counters[2]): once per step, before its first recurrent launch
 int recurrent_clear_error(unsigned* counters, hipStream_t stream);
 // shared-device mode: persistent launches take an inter-process lease (flock on a per-device file)

@@ -694,7 +694,10 @@ __device__ __forceinline__ void static_for(F&& f)
     static_for_seq(std::make_integer_sequence<int, N>(), static_cast<F&&>(f));
 }
 
-template <int NCQ, int NREGF, int NT, int NBAT, int R, int PUB, int PB, int UG = 2>
+// HALF (REC_V_T_HALF; UG = 2, NT = 1, 17..32 utterances): BOTH utterance tiles of a direction on this workgroup -- combo =
+// direction, tile = sub-chain, grid = 2 directions x H/32 unit blocks (114 at H = 1824, 128 at H = 2048).  Per CU it is the work
+// of the 33..64 form; the engine runs it while weight-gradient GEMMs have the other CUs (brnn_engine.hip, run_backward).
+template <int NCQ, int NREGF, int NT, int NBAT, int R, int PUB, int PB, int UG = 2, int HALF = 0>
 __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
 {
     extern __shared__ __attribute__((aligned(16))) float4 lds4[];
@@ -706,6 +709,7 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
     // slot q % 64 at word (q / 64) * NC, so one 16-byte load of slot `lane` still holds everything a lane checks
     constexpr int NPL = UG == 1 ? 2 : 1;
     static_assert(UG == 1 || UG == 2, "16 or 32 units per block");
+    static_assert(!HALF || (UG == 2 && NT == 1), "both tiles of a direction: 32 units, one tile per sub-chain");
     static_assert(NC <= 4 && NPL * NC <= 4, "one result per wave, one 16-byte flag load per lane");
     static_assert(NBAT % R == 0 && NBAT >= 2 * R && R >= 2, "ring");
     static_assert((NBAT - 1) * XB < NCQ, "no empty batch");
@@ -716,7 +720,9 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int Hp = p.Hp, nch = Hp >> 4, nprod = nch / UG;
     // UG == 2: combo = (direction, utterance half), four per grid; UG == 1: combo = direction, both tiles on every CU
-    const int combo = blockIdx.x & (2 * UG - 1), ublk = blockIdx.x / (2 * UG);
+    // (HALF: combo = direction, like UG == 1)
+    constexpr int NCOMBO = HALF ? 2 : 2 * UG;
+    const int combo = blockIdx.x & (NCOMBO - 1), ublk = blockIdx.x / NCOMBO;
     const int g = combo & 1, half = combo >> 1;
     const int row0 = ublk * 16 * UG;
     const int uj = lane & 15, kq = lane >> 4;
@@ -788,7 +794,7 @@ __global__ __launch_bounds__(256, 1) void brnn_recurrent_t_kernel(RecArgs p)
     auto init_sub = [&](Sub& S, int sub) {
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            const int tile = (i * 2 + sub) * UG + half;
+            const int tile = HALF ? i * 2 + sub : (i * 2 + sub) * UG + half;
             S.trow[i] = (unsigned)tile * 16u;
             S.ub[i] = tile * 16 + uj;
             S.uT[i] = S.ub[i] < p.B ? p.T_b[S.ub[i]] : 0;
@@ -1736,7 +1742,8 @@ int recurrent_supported(int Hp, int B, char* why, int why_len)
     SCTC_REC_T(X, 29, 25, 1, 8, 4, 1, 5, 2) SCTC_REC_T(X, 29, 25, 1, 6, 3, 1, 4, 2) SCTC_REC_T(X, 29, 25, 1, 8, 2, 1, 7, 2) \
     SCTC_REC_T(X, 29, 25, 2, 6, 3, 1, 4, 2) SCTC_REC_T(X, 29, 25, 2, 8, 4, 1, 5, 2) SCTC_REC_T(X, 29, 25, 2, 8, 2, 1, 7, 2) \
     SCTC_REC_T(X, 32, 31, 1, 8, 4, 1, 5, 2) SCTC_REC_T(X, 32, 31, 1, 6, 3, 1, 4, 2)                             \
-    SCTC_REC_T(X, 32, 31, 2, 8, 4, 1, 5, 2) SCTC_REC_T(X, 32, 31, 2, 6, 3, 1, 4, 2)
+    SCTC_REC_T(X, 32, 31, 2, 8, 4, 1, 5, 2) SCTC_REC_T(X, 32, 31, 2, 6, 3, 1, 4, 2)                             \
+    SCTC_REC_T(X, 29, 25, 1, 8, 4, 1, 5, 2, 1) SCTC_REC_T(X, 32, 31, 1, 8, 4, 1, 5, 2, 1)   /* REC_V_T_HALF */
 
 static RecKernel rec_kernel(const RecCandidate& c)
 {
@@ -1834,6 +1841,7 @@ struct LaunchCtx {
     hipStream_t stream;
     int* path;      // out: REC_PATH_* of the last launch
     int tcfg;       // SCTC_REC_TCFG
+    RecBeside* beside;      // nullable (recurrent.h)
 };
 
 static int read_error_word(const RecArgs& a, hipStream_t stream, unsigned* e)
@@ -1878,6 +1886,10 @@ static int launch_persistent(RecKernel k, int grid, size_t smem, int max_per_cu,
         return SCTC_OK;
     }
     SCTC_TRY(g_gate.admit_and_launch(cx.dev, cx.stream, need_cus, cx.cus, [&]() -> int {
+        if (cx.beside && !cx.beside->called && smem >= REC_LDS_EXCLUDES_GEMM) {
+            cx.beside->called = 1;
+            SCTC_TRY(cx.beside->fn(cx.beside->ctx));
+        }
         hipLaunchKernelGGL(k, dim3(grid), dim3(REC_THREADS), smem, cx.stream, a);
         SCTC_HIP_TRY(hipGetLastError());
         return SCTC_OK;
@@ -1922,7 +1934,7 @@ int recurrent_clear_error(unsigned* counters, hipStream_t stream)
     return SCTC_OK;
 }
 
-int launch_recurrent(const RecArgs& a_in, hipStream_t stream, int* path)
+int launch_recurrent(const RecArgs& a_in, hipStream_t stream, int* path, RecBeside* beside)
 {
     RecArgs a = a_in;
     if (a.poll_delay < 0) a.poll_delay = a.Hp > 1024 ? 5 : 0;
@@ -1942,6 +1954,8 @@ int launch_recurrent(const RecArgs& a_in, hipStream_t stream, int* path)
     cx.cus = 0;
     static const int tcfg = getenv("SCTC_REC_TCFG") ? atoi(getenv("SCTC_REC_TCFG")) : 0;
     cx.tcfg = tcfg;
+    cx.beside = nullptr;
+    if (beside) beside->called = 0;
     SCTC_HIP_TRY(hipGetDevice(&cx.dev));
     SCTC_HIP_TRY(hipDeviceGetAttribute(&cx.cus, hipDeviceAttributeMultiprocessorCount, cx.dev));
     // utterances are independent: more than 128 run as consecutive launches of <= 128 (sorted by
@@ -1955,6 +1969,7 @@ int launch_recurrent(const RecArgs& a_in, hipStream_t stream, int* path)
         c.B = nb;
         if (a_in.T_host) c.Tmax = std::min(a_in.Tmax, (int)a_in.T_host[b0]);
         if (c.variant == REC_V_NO_CUT) c.variant = REC_V_AUTO;
+        cx.beside = (b0 == 0 && nb == a_in.B) ? beside : nullptr;
         SCTC_TRY(launch_recurrent_one(c, cx));
         b0 += nb;
     }

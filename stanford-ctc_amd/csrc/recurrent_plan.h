@@ -21,6 +21,10 @@ enum RecVariant : int32_t {
     REC_V_SLAB_LARGE = 47,     // more than 32 utterances on the one-slab-per-CU kernel (default at 1824 / 2048 units: the tiled kernel)
     REC_V_T_SMALL = 50,        // the tiled kernel above 32 utterances at 512 / 1024 units as well (no faster there; tests)
     REC_V_Q_AT_32 = 51,        // 17..32 utterances on the two-chain kernel (default at 1824 / 2048 units, fp32: the tiled kernel, UG = 1)
+    // The BPTT launch that the engine runs weight-gradient GEMMs beside (bwd_overlap_plan.h; fp32, 17..32 utterances, 1824 / 2048
+    // units -- anywhere else both mean REC_V_AUTO).  Either form claims so much LDS that no GEMM block fits next to its workgroup.
+    REC_V_T_HALF = 52,         // the tiled kernel with 32 units x both utterance tiles of a direction per CU: half the grid, Hp / 16 CUs
+    REC_V_T_CLAIM = 53,        // the default kernel (UG = 1, Hp / 8 CUs) with the larger LDS claim
     // bit-identical A/Bs that tests use as references
     REC_V_NO_PIPE = 40,        // more than 32 utterances on the one-slab-per-CU kernel without its load / MFMA pipelining
     REC_V_ROW_MAJOR = 46,      // exchange tiles row-major throughout instead of the lane-order layout
@@ -33,7 +37,7 @@ enum RecVariant : int32_t {
 static inline bool rec_variant_known(int v)
 {
     for (int known : {REC_V_AUTO, REC_V_SLAB, REC_V_FALLBACK, REC_V_S_TO_8, REC_V_Q_FROM_1, REC_V_NO_CUT, REC_V_SLAB_LARGE,
-                      REC_V_T_SMALL, REC_V_Q_AT_32, REC_V_NO_PIPE, REC_V_ROW_MAJOR, REC_V_Q_LINEAR, REC_V_Q_PRIO_DIR,
+                      REC_V_T_SMALL, REC_V_Q_AT_32, REC_V_T_HALF, REC_V_T_CLAIM, REC_V_NO_PIPE, REC_V_ROW_MAJOR, REC_V_Q_LINEAR, REC_V_Q_PRIO_DIR,
                       REC_V_Q_PRIO_TILE, REC_V_Q_PRIO_PARITY, REC_V_T_STALE})
         if (v == known) return true;
     return false;
@@ -50,14 +54,14 @@ enum RecFamily {
     REC_FAM_Q,          // brnn_recurrent_q_kernel<NCQ, NREG>: flag / MFMA kernel, one or two chains per direction
     REC_FAM_S,          // brnn_recurrent_s_kernel<NK, SB>: sentinel / VALU kernel
     REC_FAM_MH,         // brnn_recurrent_mh_kernel<NCH, BF>: sentinel / MFMA kernel, 16-bit operands
-    REC_FAM_T,          // brnn_recurrent_t_kernel<NCQ, NREGF, NT, NBAT, R, PUB, PB, UG>: tiled over units x utterances
+    REC_FAM_T,          // brnn_recurrent_t_kernel<NCQ, NREGF, NT, NBAT, R, PUB, PB, UG[, HALF]>: tiled over units x utterances
     REC_FAM_SLAB,       // brnn_recurrent_kernel<NTW, NCHH, PIPE>: one 16-unit slab per CU
     REC_FAM_FALLBACK,   // brnn_recurrent_step_kernel, one launch per time step: always the plan's last candidate
 };
 
 struct RecCandidate {
     RecFamily family;
-    int ntarg, targ[8];     // template arguments, in the kernel's order
+    int ntarg, targ[9];     // template arguments, in the kernel's order
     int grid;
     size_t lds;             // dynamic LDS bytes
     int per_cu;             // workgroups of this kernel that share a CU
@@ -65,7 +69,7 @@ struct RecCandidate {
     int linear_map;         // RecArgs.linear_map
     int variant;            // RecArgs.variant as the kernel sees it
 };
-static constexpr int REC_MAX_CANDIDATES = 5;    // at most two of Q / S / MH / T, then SLAB, then the fallback (one spare)
+static constexpr int REC_MAX_CANDIDATES = 6;    // at most two of Q / S / MH / T (REC_V_T_HALF: three), then SLAB, then the fallback (one spare)
 
 // The per-layer-size facts.
 // <weight fragments in registers, batches per phase, ring depth, publish batch, batch in front of which the next
@@ -103,6 +107,9 @@ static inline const RecSize* rec_size(int Hp)
 
 // dynamic LDS of each family
 static constexpr size_t REC_LDS_MAX = 160 * 1024, REC_F4 = 16;    // LDS of a CU; sizeof(float4)
+// A workgroup that claims this much leaves less than any fp32 GEMM block needs (the smallest takes 25 KiB, gemm_plan.h;
+// tests/test_bwd_overlap_plan_cpu.py): GEMM blocks of a concurrent launch go to the CUs this grid does not occupy.
+static constexpr size_t REC_LDS_EXCLUDES_GEMM = REC_LDS_MAX - 16 * 1024;
 // the LDS share of the wave-private weight fragments + the K-quarter partial sums of three waves
 static inline size_t rec_lds_q(const RecSize& r) { return REC_F4 * ((size_t)4 * (r.ncq - r.nreg) * 64 + 3 * 64); }
 static inline size_t rec_lds_s(int Hp, int sb) { return sizeof(float) * 2 * sb * Hp; }
@@ -134,9 +141,13 @@ static inline RecCandidate rec_candidate_t(const RecShape& s, const RecSize& r, 
 
 // The candidates of one launch (s.B <= 128 utterances) in the order they are tried; the launcher skips a candidate the
 // device cannot co-reside.  Returns their number, or -1 for a variant that does not exist.
-static inline int rec_plan(const RecShape& s, RecCandidate out[REC_MAX_CANDIDATES])
+static inline int rec_plan(const RecShape& s_in, RecCandidate out[REC_MAX_CANDIDATES])
 {
-    if (!rec_variant_known(s.variant)) return -1;
+    if (!rec_variant_known(s_in.variant)) return -1;
+    // the two overlap forms are the default plan with one candidate put in front (half grid) or its LDS claim raised
+    RecShape s = s_in;
+    const bool t_half = s_in.variant == REC_V_T_HALF, t_claim = s_in.variant == REC_V_T_CLAIM;
+    if (t_half || t_claim) s.variant = REC_V_AUTO;
     const int nwg = s.Hp / 16, ntiles = (s.B + 15) / 16, v = s.variant, B = s.B, sb = B <= 4 ? 4 : 8;
     const RecSize* r = rec_size(s.Hp);
     const int tcfg = s.tcfg >= 0 && s.tcfg <= 3 ? s.tcfg : 0;
@@ -160,8 +171,16 @@ static inline int rec_plan(const RecShape& s, RecCandidate out[REC_MAX_CANDIDATE
         out[n++] = rec_candidate(s, REC_FAM_MH, {r->nch, s.transpose != 0}, 2 * nwg, rec_lds_mh(s.Hp), 1, 2);
     // 17..32 utterances, fp32, H = 1824 / 2048: the tiled kernel with 16 units x both utterance tiles of a direction per CU.  With its
     // slab in registers a second workgroup would fit a CU: more than half of the LDS is claimed (the co-residency check counts CUs)
+    // REC_V_T_HALF: the 33..64 form (32 units, two alternating sub-chains) with combo = direction, tile = sub-chain, on
+    // 2 * Hp / 32 CUs; its slab takes 144 KiB of LDS by itself.  The default schedule only (one instantiation per layer size).
+    if (t_half && persistent && r && r->t_default && ntiles == 2 && !s.prec16) {
+        RecCandidate c = rec_candidate_t(s, *r, r->t_one[0], 1, 2, REC_LDS_EXCLUDES_GEMM);
+        c.targ[c.ntarg++] = 1;      // HALF
+        c.grid = 2 * (s.Hp / 32);
+        out[n++] = c;
+    }
     if (persistent && r && r->t_ug1[tcfg].nbat && ntiles == 2 && !s.prec16 && (v == REC_V_AUTO || v == REC_V_ROW_MAJOR || v == REC_V_T_STALE))
-        out[n++] = rec_candidate_t(s, *r, r->t_ug1[tcfg], 1, 1, (size_t)81 * 1024);
+        out[n++] = rec_candidate_t(s, *r, r->t_ug1[tcfg], 1, 1, t_claim ? REC_LDS_EXCLUDES_GEMM : (size_t)81 * 1024);
     // two chains per CU
     if (persistent && r && ntiles == 2 && v != REC_V_SLAB && 4 * nwg <= 2 * s.cus)
         out[n++] = rec_candidate(s, REC_FAM_Q, {r->ncq, r->nreg}, 4 * nwg, rec_lds_q(*r), 2, 0);

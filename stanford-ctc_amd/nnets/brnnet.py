@@ -568,6 +568,11 @@ class NNet:
                                                          ctypes.byref(r)), "recurrentPath")
         return f.value, b.value, r.value
 
+    def bwdOverlapMode(self):
+        """which order the last backward pass ran in: 0 serial, 1 / 2 the weight gradients above the temporal layer beside
+        the default / the half-grid BPTT (SCTC_BWD_OVERLAP)"""
+        return int(_sctc.lib().sctc_brnn_bwd_overlap_mode(self._h))
+
     def debugBuffer(self, which):
         """diagnostics: host copy (float64, [rows][cols]) of an internal matrix of the last call --
         which: 0..numLayers = hActs[i], 100 / 101 = hActsFor / hActsBack, 102 = the temporal layer's W h + b, 200 = delta entering
